@@ -1,15 +1,22 @@
 #!/usr/bin/env python
 """Benchmark of the MERLOT Reserve pretraining step on MI355X (contract: see the task's bench.py section).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--model base|large] [--records-per-gpu B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--model base|large] [--records-per-gpu B] [--full] [--dump-outputs DIR]
 
 One "step" = one full pretraining step (plan + forward + contrastive loss + backward + gradient all-reduce + fused
 bf16-Adam update) on B records (= 2B video-segment groups of 8 frames) per GPU of synthetic data already resident in
 HBM.  N > 1: one rank per GPU under torch.distributed.run (started by the driver, or by this script itself when it is
 invoked bare), collectives on the library's RCCL communicator over xGMI inside the step's hipGraph, weak scaling.
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the bf16 MFMA GEMM): algorithmic FLOPs of its
-launches / their HIP-event durations, measured in an instrumented pass of the same steps right after the timed region;
-`cpu_baseline` times the oracle (a CPU port of the reference's step) on a bounded sample, rank 0, N=1 only.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints
+the line (value, ms_per_step and the cheap fields of `config`); everything else the benchmark measures or checks runs only with
+--full: the graph == eager check, the calibration kernels around the timed region, the host-fed pass, the bucket timeline
+(N > 1), `roofline` / `breakdown`, `config.secondary` and `cpu_baseline` (the --no-* switches still drop single items of it).
+`roofline` is for the dominant kernel (the bf16 MFMA GEMM): algorithmic FLOPs of its launches / their HIP-event durations,
+measured in an instrumented pass of the same steps right after the timed region; `cpu_baseline` times the oracle (a CPU
+port of the reference's step) on a bounded sample, rank 0, N=1 only.
+--dump-outputs DIR: after the timed steps, what the last timed step computed -- the loss terms, the forward's contrastive
+embeddings, and a fixed seeded sample of the updated fp32 master parameters and Adam moments -- as DIR/<name>.npy (float32 /
+float64, < 64 MB in all), so that two builds can be compared output for output on identical (seeded) inputs.
 """
 import argparse
 import json
@@ -20,7 +27,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-MFMA_BF16_PEAK = 2.5e15      # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_BF16_PEAK = 2.5e15      # dense bf16 MFMA peak, MI355X_MICROARCH.md
 
 
 def algorithmic_flops_per_record(config, train=True):
@@ -220,6 +227,46 @@ def secondary_configs(dev, replays=6, warm=3):
     return res
 
 
+DUMP_SAMPLE = 1 << 21            # parameter entries per sampled vector (8.4 MB as float32)
+DUMP_ROWS = 1 << 10              # rows per sampled embedding section
+DUMP_LIMIT = 64 * 10 ** 6        # bytes, all files together
+
+
+def dump_outputs(trainer, info, out_dir):
+    """What the last timed step handed its caller, as out_dir/<name>.npy: the loss terms (`loss_info.<key>`, float64), the contrastive
+    embeddings of the forward (`preds.<objective>.<x|y|y_extra>`, float32, at most DUMP_ROWS rows each, a fixed seeded row sample), and
+    the updated state at one fixed seeded sample of DUMP_SAMPLE flat parameter indices: the fp32 master parameters and the two bf16 Adam
+    moments as stored (`adam_nu` is the optimizer's unsigned bf16 encoding, read as a bf16 value).  The samples depend only on the sizes,
+    so two builds of the same model pick the same entries.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f'loss_info.{k}': np.asarray(v, dtype=np.float64) for k, v in sorted(info.items())}
+    for obj, d in sorted(trainer.engine.outputs().items()):
+        for k, v in sorted(d.items()):
+            if k.startswith('_'):                # host-side plan data, not a result
+                continue
+            v = v.detach()
+            if v.shape[0] > DUMP_ROWS:
+                rows = np.sort(np.random.default_rng(1).choice(v.shape[0], DUMP_ROWS, replace=False))
+                v = v[torch.as_tensor(rows, device=v.device)]
+            arrays[f'preds.{obj}.{k}'] = v.float().cpu().numpy()
+    p = trainer.params
+    n = p.total
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    idx = torch.as_tensor(idx, device=p.master.device)
+    arrays['params.master'] = p.master[idx].float().cpu().numpy()
+    for k in ('mu', 'nu'):
+        if getattr(p, k, None) is not None:
+            arrays[f'adam_{k}'] = getattr(p, k)[idx].float().cpu().numpy()
+    total = sum(a.nbytes + 128 for a in arrays.values())           # + the .npy header
+    assert total <= DUMP_LIMIT, f'--dump-outputs: {total} bytes > {DUMP_LIMIT}'
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def _self_launch(args, argv):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start N fresh ranks under torch.distributed.run as a
     CHILD process (this process has not touched the GPU and never execs), pass rank 0's JSON line through, return its code."""
@@ -235,7 +282,7 @@ def _self_launch(args, argv):
     return subprocess.run(cmd, env=env).returncode
 
 
-def main():
+def _parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
@@ -253,7 +300,17 @@ def main():
     ap.add_argument('--no-secondary', action='store_true', help='skip the short timings of BASELINE configs 3-5 (large, large resadapt, VCR large) at N = 1')
     ap.add_argument('--option', action='append', default=[], metavar='NAME=VALUE', help='library option for this run (mr_set_option; A/B of kernel paths), e.g. --option attn_onepass=0')
     ap.add_argument('--comm', default='native', choices=['native', 'torch'], help="native: the library's RCCL communicator (captured into the hipGraph); torch: torch.distributed nccl (eager step)")
+    ap.add_argument('--full', action='store_true', help='also run every measurement and check beside the headline: graph == eager check, calibration, host-fed pass, '
+                                                       'bucket timeline (N > 1), roofline / breakdown, secondary configs, CPU baseline (the --no-* switches drop single items)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    return ap
+
+
+def main():
+    ap = _parser()
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(_self_launch(args, sys.argv[1:]))
@@ -351,7 +408,7 @@ def main():
     # one-shot check of the captured program against the eager one, from the SAME parameter / optimizer state and batch: the loss and every
     # master parameter after the step must agree bit for bit on every rank (a bad multi-rank capture reports itself instead of being timed)
     graph_equals_eager = None
-    if use_graph:
+    if use_graph and args.full:
         p_ = trainer.params
         snap = {k: getattr(p_, k).clone() for k in ('master', 'mu', 'nu')}
         step0 = trainer.state.step
@@ -378,15 +435,16 @@ def main():
             degraded.append('the captured hipGraph step does NOT reproduce the eager step (loss / master parameters differ on some rank): the timed program is suspect')
         restore()
         del snap, ref_master
-    calib = [calibrate(dev)] if rank == 0 and not args.no_calibration else []
-    calib_hbm = [calibrate_hbm(dev)] if rank == 0 and not args.no_calibration else []
+    with_calib = rank == 0 and args.full and not args.no_calibration
+    calib = [calibrate(dev)] if with_calib else []
+    calib_hbm = [calibrate_hbm(dev)] if with_calib else []
     run(args.warmup)
     barrier()
     t0 = time.perf_counter()
     run(args.steps)
     barrier()
     dt = time.perf_counter() - t0
-    if rank == 0 and not args.no_calibration:
+    if with_calib:
         calib.append(calibrate(dev))
         calib_hbm.append(calibrate_hbm(dev))
         if abs(calib[0] - calib[1]) > 0.03 * max(calib):
@@ -395,12 +453,14 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    loss = trainer.loss_info()['loss']                         # mean over ranks (a collective when world > 1)
+    info = trainer.loss_info()                                 # mean over ranks (a collective when world > 1)
+    loss = info['loss']
+    dumped = dump_outputs(trainer, info, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # the same steps with the inputs crossing PCIe every step (pinned double-buffered prefetch on a copy stream,
     # merlot_reserve_amd/loader.py = the reference's prefetch_to_device): reported beside `value`, never as it
     h2d_ms = None
-    if use_graph and not args.no_h2d:
+    if use_graph and args.full and not args.no_h2d:
         import itertools
         from merlot_reserve_amd.loader import PrefetchLoader
         host = [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in b.items()} for b in batches]
@@ -419,7 +479,7 @@ def main():
     # optimizer update ended, against the end of backward on the main stream -- so that the first run on a multi-GPU node shows by
     # itself whether the collectives hide under backward (the graph-replayed steps above cannot be instrumented)
     timeline = None
-    if comm is not None:
+    if comm is not None and args.full:
         try:
             timeline = trainer.train_step_timeline(batches[0])
         except Exception as e:                                   # a diagnostic must not cost the benchmark line
@@ -454,7 +514,7 @@ def main():
         barrier()
 
     roof, breakdown = None, None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         nprof = min(args.steps, 3)
         ops.GEMM_PROFILE = []
         run(nprof, graph=False)
@@ -584,12 +644,14 @@ def main():
                        'calibration_hbm_tbs': [round(c_, 3) for c_ in calib_hbm],       # (round 6) mr_add_bf16 over 1.15 GB per launch before / after the timed region: the box's memory speed
                        'calibration_note': 'shipped plain NT mr_gemm at 8192^3 (gaussian bf16), ~50 ms of back-to-back launches before / after the timed region; '
                                            'compare rounds and boxes by ms_per_step x mean(calibration_tflops)',
-                       'graph_equals_eager': graph_equals_eager,
+                       'graph_equals_eager': graph_equals_eager, 'full': bool(args.full),
                        'step_mfma_frac': step_flops / (dt / args.steps) / MFMA_BF16_PEAK},
             'roofline': roof, 'breakdown': breakdown,
         }
         if args.option:
             out['config']['options'] = args.option
+        if dumped is not None:
+            out['config']['dumped_outputs'] = dumped
         if degraded:
             out['degraded'] = degraded
         if timeline is not None:
@@ -602,11 +664,11 @@ def main():
                                      'NCCL_PROTO': os.environ.get('NCCL_PROTO', 'auto (RCCL tuner)'),
                                      'allreduce_bucket_mbytes': [round((b[2] - b[1]) * 2 / 1e6, 1) for b in trainer.buckets],
                                      'allgather_mbytes_per_rank': round(trainer.engine.R * trainer.engine.d.H * 2 / 1e6, 3)}
-        if world == 1 and not args.no_secondary and comm is None:
+        if world == 1 and args.full and not args.no_secondary and comm is None:
             del trainer
             torch.cuda.empty_cache()
             out['config']['secondary'] = secondary_configs(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(config)
         print(json.dumps(out), flush=True)
     if comm is not None:

@@ -5,12 +5,12 @@ other=$1
 summ='import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 print(sys.argv[2], "ms/step", round(d["ms_per_step"],2), "calib", d["config"]["calibration_tflops"], "breakdown", d["breakdown"]["ms_per_step"])'
-mkdir -p gpurun_out/ab
+ab=${AB_DIR:-$(mktemp -d)}; mkdir -p "$ab"; echo "bench lines under $ab"
 for rep in 1 2; do
   MR_LIB=$other python scripts/attn_bench.py 2>&1 | grep -v amdgpu | sed "s/^/[other] /"
   python scripts/attn_bench.py 2>&1 | grep -v amdgpu | sed "s/^/[ours ] /"
 done
 for rep in 1 2; do
-  MR_LIB=$other python bench.py --steps 15 --warmup 5 --no-cpu-baseline --no-secondary --no-h2d > gpurun_out/ab/other$rep.json 2>/dev/null; python -c "$summ" gpurun_out/ab/other$rep.json "[other]"
-  python bench.py --steps 15 --warmup 5 --no-cpu-baseline --no-secondary --no-h2d > gpurun_out/ab/ours$rep.json 2>/dev/null; python -c "$summ" gpurun_out/ab/ours$rep.json "[ours ]"
+  MR_LIB=$other python bench.py --steps 15 --warmup 5 --full --no-cpu-baseline --no-secondary --no-h2d > $ab/other$rep.json 2>/dev/null; python -c "$summ" $ab/other$rep.json "[other]"
+  python bench.py --steps 15 --warmup 5 --full --no-cpu-baseline --no-secondary --no-h2d > $ab/ours$rep.json 2>/dev/null; python -c "$summ" $ab/ours$rep.json "[ours ]"
 done

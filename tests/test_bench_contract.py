@@ -55,3 +55,44 @@ def test_gemm_algorithmic_bytes():
     assert ops.gemm_bytes(g) == 2 * (256 * 128 + 512 * 128) + 2 * 256 * 512
     g = types.SimpleNamespace(M=256, N=512, K=128, c_dtype=ops.MR_DT_F32, c2=1, residual=1, aux=None, bias=1)
     assert ops.gemm_bytes(g) == 2 * (256 * 128 + 512 * 128) + 4 * 256 * 512 + 2 * 2 * 256 * 512 + 2 * 512
+
+
+def test_plain_run_options():
+    """--full (every measurement and check beside the headline) is off by default; --dump-outputs names a directory."""
+    bench = _bench()
+    a = bench._parser().parse_args([])
+    assert a.full is False and a.dump_outputs is None and a.steps == 10 and a.warmup == 3 and a.gpus == 1
+    a = bench._parser().parse_args(['--full', '--dump-outputs', 'out', '--steps', '7'])
+    assert a.full is True and a.dump_outputs == 'out' and a.steps == 7
+
+
+def test_dump_outputs_files(tmp_path):
+    """dump_outputs on host tensors shaped like the step's: float32 / float64 .npy files under the 64 MB cap, the parameter sample and the
+    embedding rows chosen by fixed seeds (the same entries on every call), the plan's host data left out."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    n, H = 3 * bench.DUMP_SAMPLE + 5, 768
+    g = torch.Generator().manual_seed(0)
+    master = torch.randn(n, generator=g)
+    params = types.SimpleNamespace(total=n, master=master, mu=master.to(torch.bfloat16), nu=(master * 0.5).to(torch.bfloat16))
+    E = torch.randn(6000, H, generator=g).to(torch.bfloat16)
+    outs = {'imgs_to_audio': {'x': E[:2000], 'y': E[2000:4000]},
+            'text_to_audio': {'x': E[:500], 'y': E[500:5000], 'y_extra': E[5000:]},
+            'stuff_to_span': {'x': E[:100], 'y': E[100:300], '_sources': torch.arange(3)}}
+    tr = types.SimpleNamespace(params=params, engine=types.SimpleNamespace(outputs=lambda: outs))
+    info = {'loss': 1.25, 'imgs_to_audio': 0.5}
+    shapes = bench.dump_outputs(tr, info, str(tmp_path / 'a'))
+    bench.dump_outputs(tr, info, str(tmp_path / 'b'))
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(k + '.npy' for k in shapes) and 'preds.stuff_to_span._sources.npy' not in files
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64e6
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    assert float(np.load(tmp_path / 'a' / 'loss_info.loss.npy')) == 1.25
+    m = np.load(tmp_path / 'a' / 'params.master.npy')
+    assert m.shape == (bench.DUMP_SAMPLE,) and np.isin(m, master.numpy()).all()
+    assert np.array_equal(np.load(tmp_path / 'a' / 'adam_mu.npy'), torch.as_tensor(m).to(torch.bfloat16).float().numpy())
+    assert np.load(tmp_path / 'a' / 'preds.text_to_audio.y.npy').shape == (bench.DUMP_ROWS, H)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'preds.stuff_to_span.y.npy'), E[100:300].float().numpy())

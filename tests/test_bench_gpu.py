@@ -1,11 +1,13 @@
 """bench.py end to end on the GPU (a child process, few steps): the ONE JSON line the driver parses carries every field of the
 contract -- metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data /
-config.workload, the roofline object (bound, achieved, peak, unit, frac, traffic) and the per-family breakdown."""
+config.workload, and with --full the roofline object (bound, achieved, peak, unit, frac, traffic) and the per-family breakdown.  A plain
+run is the headline alone, and --dump-outputs writes the last timed step's results."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_contract(dev):
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-h2d']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-h2d']
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
@@ -56,7 +58,7 @@ def test_bench_line_contract(dev):
 def test_bench_multi_rank_code_path_with_one_rank(dev):
     """--force-comm: the N > 1 program (gloo control plane, the library's RCCL communicator, all-gather / reduce-scatter / five bucket
     all-reduces captured inside the step's graph) with a single rank -- what can be rehearsed on a 1-GPU box."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-h2d',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-h2d',
            '--no-roofline', '--force-comm']
     import socket
     with socket.socket() as sk:
@@ -73,3 +75,37 @@ def test_bench_multi_rank_code_path_with_one_rank(dev):
     assert d['value'] > 0 and d['n_gpus'] == 1
     assert c['graph_equals_eager'] is True, 'the one-shot check of the captured multi-rank program against the eager step'
 
+
+def _plain_run(out_dir, steps):
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1', '--dump-outputs', str(out_dir)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_and_dumped_outputs(dev, tmp_path):
+    """Without --full the line is the headline alone (no roofline / breakdown / calibration / graph == eager check / secondary configs /
+    CPU baseline); --steps sets the timed steps; --dump-outputs leaves float32 / float64 .npy files, < 64 MB together, and two runs of the
+    same command see the same seeded inputs and compute the same results, bit for bit (fixed-order reductions; the graph == eager check rests on the same property)."""
+    d = _plain_run(tmp_path / 'a', 2)
+    assert d['metric'].startswith('video-segments/sec') and d['unit'] == 'video-segments/sec' and d['higher_is_better'] is True
+    assert d['dtype'] == 'bf16' and d['steps'] == 2 and d['warmup'] == 1 and d['ms_per_step'] > 0
+    assert abs(d['value'] - 8 * 1000.0 / d['ms_per_step']) < 1e-6 * d['value']
+    c = d['config']
+    assert c['full'] is False and c['hipgraph'] is True and 'degraded' not in d
+    assert d['roofline'] is None and d['breakdown'] is None and 'cpu_baseline' not in d and 'secondary' not in c
+    assert c['calibration_tflops'] == [] and c['graph_equals_eager'] is None and c['ms_per_step_inputs_from_host'] is None
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert set(f[:-4] for f in files) == set(c['dumped_outputs']) and all(f.endswith('.npy') for f in files)
+    assert {'loss_info.loss.npy', 'params.master.npy', 'adam_mu.npy', 'adam_nu.npy', 'preds.imgs_to_audio.x.npy'} <= set(files)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64e6
+    a = {f: np.load(tmp_path / 'a' / f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert float(a['loss_info.loss.npy']) == c['final_loss'] and np.isfinite(a['params.master.npy']).all()
+    _plain_run(tmp_path / 'b', 2)
+    assert sorted(os.listdir(tmp_path / 'b')) == files
+    for f in files:
+        b = np.load(tmp_path / 'b' / f)
+        assert a[f].shape == b.shape and np.array_equal(a[f], b), f
