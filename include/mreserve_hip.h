@@ -53,7 +53,6 @@ const char* mr_last_error(void);
  * Option names:
  *   "gemm_tile_n"   0 = choose per problem (default) | 96 | 128 | 192 | 256 : forces the output-tile width of the 256-row GEMM
  *   "gemm_group_tile_n"  0 = choose (default) | 128 | 256 : tile width of mr_gemm_grouped's shared launch
- *   "gemm_v1_only"  1 = route every GEMM to the small-tile kernel
  *   "gemm3"         1 = default: NT problems with enough tiles run on the ping-pong kernel (gemm3.hip) | 0 = off | 256 / 192 = on
  *                   for EVERY NT problem it can take, with that tile width (tests, A/B)
  *   "gemm3_phases"  0 = choose per problem (default) | 1 | 2 : barrier phases per k-tile of the ping-pong kernel (tests, A/B)
@@ -64,8 +63,7 @@ const char* mr_last_error(void);
  *                   "gemm3" admits
  *   "gemm5"         -1 = default: the few-tile problems (gemm5.hip: at most one 128 x 128 tile per CU -> that geometry; at most one
  *                   256 x 128 tile per CU and K <= 1024 -> two workgroups per CU) | 0 = never | 1 = every NT problem it can take on 256 x 128
- *                   tiles | 3 = on 128 x 128 tiles (tests, A/B);  "gemm5_stagger"  -1 = default | 0..3 : the
- *                   start phase of two workgroups sharing a CU
+ *                   tiles | 3 = on 128 x 128 tiles (tests, A/B)
  *   "attn_onepass"  -1 = default: mr_attention_bwd runs its one-pass kernel (dQ, dK, dV from one sweep, one workgroup per (sequence,
  *                   head)) for 128 < S <= 256 | 0 = never (the dQ + dK / dV kernel pair) | 1 = whenever S <= 256 (tests, A/B)
  *   "attn_tile_modes" 1 = default: the masked attention kernels classify every (wave, 64-position tile) pair by the position codes -- all pairs
@@ -74,10 +72,6 @@ const char* mr_last_error(void);
  *   "gemm_trace"    1 = every GEMM launch records the kernel it was routed to (mr_last_gemm_kernel; bench.py's per-kernel table)
  *   "ln_impl"       1 = default: mr_layernorm_bwd runs the round-6 kernel (<= 128 registers, 512-thread workgroups: the whole grid resident; at most
  *                   512 partial rows) | 0 = round 5's (A/B).  mr_layernorm_bwd_nparts follows the option.
- *   "gemm_xpx"      0 = default: the XCD partition px x (8 / px) of a persistent GEMM's tile grid comes from the cost model | 1 | 2 | 4 | 8 forces px;
- *   "gemm_xpanel"   0 = default (8): tile columns per panel of an XCD cell's walk (experiment knobs: scripts/xcd_walk_ab.sh)
- * Environment variables (MR_GEMM3, MR_G3_PH, ...: experiment scripts) are read only by a library built with -DMR_DEBUG_ENV
- * (MR_DEBUG_ENV=1 python -m merlot_reserve_amd.build); the product build ignores the environment.
  * Unknown names return MR_EINVAL. */
 typedef struct mr_handle_s* mr_handle;
 int mr_create(int32_t device, int64_t ws_bytes, mr_handle* out);

@@ -29,7 +29,7 @@ EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'layernorm.hip': ['-fno-
 # object is kept under build/ (a by-product of the object's own compile, --save-temps) and build() fails if such an instruction appears.
 SLP_FILES = ['gemm.hip', 'gemm256.hip', 'gemm3.hip', 'gemm4.hip', 'gemm5.hip']        # the files that keep the SLP vectoriser (packed epilogues)
 HAZARD_RE = r'^\s*v_pk_(add|mul|fma|min|max)_f32\b.*\bop_sel:\['
-SOURCES = ['gemm.hip', 'gemm256.hip', 'gemm3.hip', 'gemm4.hip', 'gemm5.hip', 'attention.hip', 'layernorm.hip', 'rowops.hip', 'adam.hip', 'f32path.hip', 'f32bwd.hip', 'mr_error.cpp', 'comm.cpp', 'hostio.cpp']
+SOURCES = ['gemm.hip', 'gemm256.hip', 'gemm3.hip', 'gemm4.hip', 'gemm5.hip', 'gemm_route.cpp', 'attention.hip', 'layernorm.hip', 'rowops.hip', 'adam.hip', 'f32path.hip', 'f32bwd.hip', 'mr_error.cpp', 'comm.cpp', 'hostio.cpp']
 HIP_FILES = [f for f in SOURCES if f.endswith('.hip')]
 # Register spills (metadata .vgpr_spill_count / .sgpr_spill_count of every kernel in the device assembly): a spill inside a k-loop costs more than any
 # schedule gains (gemm4<256,0> with 183 spilled registers: 299 vs 91 us), so build() FAILS on a kernel with spilled vector registers unless it is
@@ -55,9 +55,8 @@ JOBS = max(1, min(8, (os.cpu_count() or 2)))
 
 
 def _flag_stamp():
-    """What the objects under build/ were compiled with: a rebuild is needed when it differs (e.g. MR_DEBUG_ENV toggled), not only when a source is newer."""
-    debug = os.environ.get('MR_DEBUG_ENV') == '1'
-    return 'debug_env=%d\n' % debug + ''.join(f'{k}: {" ".join(v)}\n' for k, v in sorted(EXTRA_FLAGS.items()))
+    """What the objects under build/ were compiled with: a rebuild is needed when it differs (e.g. EXTRA_FLAGS changed), not only when a source is newer."""
+    return ''.join(f'{k}: {" ".join(v)}\n' for k, v in sorted(EXTRA_FLAGS.items()))
 
 
 def _asm_path(src):
@@ -177,16 +176,13 @@ def build(force=False, verbose=True):
         return LIB
     import json
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    # MR_DEBUG_ENV=1: a DEBUG build whose kernels' dispatch reads the experiment scripts' environment knobs (MR_GEMM3, MR_G3_PH, ...:
-    # csrc/mr_options.h mr_env_int); the product build ignores the environment
-    debug = ['-DMR_DEBUG_ENV'] if os.environ.get('MR_DEBUG_ENV') == '1' else []
     bdir = os.path.join(HERE, 'build')
     os.makedirs(bdir, exist_ok=True)
     objs, queue, running, failed = [], [], [], []
     for src in SOURCES:
         stem = src.rsplit('.', 1)[0]
         obj = os.path.join(bdir, stem + '.o')
-        cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17'] + debug + EXTRA_FLAGS.get(src, []) + ['-x', 'hip', '-c', os.path.join(CSRC, src), '-o', obj]
+        cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17'] + EXTRA_FLAGS.get(src, []) + ['-x', 'hip', '-c', os.path.join(CSRC, src), '-o', obj]
         if src.endswith('.hip'):
             cmd.append('--save-temps=obj')          # leaves <stem>-hip-amdgcn-amd-amdhsa-gfx950.s: the device assembly OF THIS OBJECT, for the scans
         queue.append((src, cmd))

@@ -36,45 +36,10 @@
 #include "mr_common.h"
 #include "mr_options.h"
 
-// diagnostic builds (scripts/build_diag.sh): -DMR_ATTN_OCC=n / -DMR_ATTN_OCC_DQ=n set the waves per SIMD the register allocator targets
-// (the forward kernel fits three by itself since its K / V tiles are LDS-DMA staged: 162-168 registers)
-#ifndef MR_ATTN_OCC_DQ      /* masked dQ kernel: 184 registers by itself; held to three waves per SIMD it spills a few and is still faster (joint backward 181 -> 175 us) */
-#define MR_ATTN_OCC_DQ 3
-#endif
-#ifndef MR_ATTN_OCC_DQ_UNMASKED   /* unmasked dQ kernel: fits three waves per SIMD since the ragged last tile is peeled */
-#define MR_ATTN_OCC_DQ_UNMASKED 3
-#endif
-#ifndef MR_ATTN_OCC
-#define MR_ATTN_OCC 2
-#endif
-// -DMR_ATTN_STAMPS (diagnostic build): s_memtime stamps of the forward kernel's phases for the first tiles of the first workgroups,
-// into a buffer of their own that mr_diag_attn_stamps() copies out; no stamp executes in the product build
-#ifdef MR_ATTN_STAMPS
-#ifndef MR_ATTN_STAMP_K       /* which kernel stamps: 0 = every instrumented one (the last launch wins), 1 forward, 2 dQ, 3 dK / dV, 4 one-pass backward */
-#define MR_ATTN_STAMP_K 0
-#endif
-__device__ unsigned long long g_attn_stamps[512 * 16 * 8];
-#define MR_ASTAMP(slot)                                                                                        \
-    do {                                                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        unsigned long long t_;                                                                                 \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                             \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        if ((MR_ATTN_STAMP_K == 0 || MR_ATTN_STAMP_K == stamp_id) && lane == 0 && wave == 0 && blockIdx.x < 512 && t < 16) g_attn_stamps[(blockIdx.x * 16 + t) * 8 + (slot)] = t_; \
-    } while (0)
-// workgroup begin / end (tile row 15 of the workgroup's stamps, slots 0 / 1; the loop-top stamp of tile 0 marks the prologue's end)
-#define MR_ASTAMP_WG(slot)                                                                                     \
-    do {                                                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        unsigned long long t_;                                                                                 \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                             \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        if ((MR_ATTN_STAMP_K == 0 || MR_ATTN_STAMP_K == stamp_id) && lane == 0 && wave == 0 && blockIdx.x < 512) g_attn_stamps[(blockIdx.x * 16 + 15) * 8 + (slot)] = t_; \
-    } while (0)
-#else
-#define MR_ASTAMP(slot) do {} while (0)
-#define MR_ASTAMP_WG(slot) do {} while (0)
-#endif
+// Waves per SIMD the register allocator targets (__launch_bounds__): two for the forward and dK / dV kernels (the forward kernel fits three by
+// itself since its K / V tiles are LDS-DMA staged: 162-168 registers), three for the dQ kernels -- the masked one needs 184 registers by
+// itself; held to three waves per SIMD it spills a few and is still faster (joint backward 181 -> 175 us); the unmasked one fits three since
+// the ragged last tile is peeled.
 
 namespace {
 
@@ -221,7 +186,7 @@ __device__ __forceinline__ int rot_row_index(int seq_rot0, int pos, int rot_rows
 // A wave's [16 NB rows][64 dims] bf16 tile, held as the MFMA leaves it (lane: dims 16 db + 4 g .. + 3 of row 16 nb + i), to global memory as WHOLE
 // 128-byte rows, 16 bytes per lane, through a 2 NB KiB LDS region private to the wave ([row][128 B], 16-byte chunk c of row r at slot c ^ (r & 7)).  Stored
 // straight from the MFMA layout a wave instruction wrote 16 rows x 32 bytes -- 16 partial lines: 7 900 of the one-pass backward's 61 000 cycles per
-// workgroup (scripts/attn_bwd1_stamps.py).  Row `row0 + r` goes to gdst + r * ld (elements) if it is < n_rows.  No barrier: the wave's own waits order it.
+// workgroup (in-kernel stamps).  Row `row0 + r` goes to gdst + r * ld (elements) if it is < n_rows.  No barrier: the wave's own waits order it.
 template <int NB>
 __device__ __forceinline__ void store_rows_via_lds(char* stg, const bf16x4 (&v)[NB][4], __bf16* gdst, int64_t ld, int row0, int64_t n_rows, int lane) {
     const int g = lane >> 4, i = lane & 15;
@@ -268,7 +233,7 @@ constexpr float NEG_BIG2 = -1e10f * LOG2E;         // the reference's -1e10 bias
 
 // ------------------------------------------------------------------------------------------------ forward
 template <int QB, bool MASKED>
-__global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_fwd_kernel(const __bf16* __restrict__ qkv, const int32_t* __restrict__ code,
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const __bf16* __restrict__ qkv, const int32_t* __restrict__ code,
                                                           __bf16* __restrict__ out, float* __restrict__ lse,
                                                           int64_t S, int64_t nh, const int tile_modes) {
     __shared__ __attribute__((aligned(16))) char Ks[2][TILE_B];          // LDS-DMA images (see dma_src)
@@ -276,14 +241,12 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_fwd_kernel(const __bf16
     // key codes (masked), the additive key bias (exp2 domain, see key_meta2) and the tile classes of the WHOLE sequence: dynamic LDS, written once in the
     // prologue by all four waves (8 bytes per padded position + 4 per tile) -- see the dQ kernel
     extern __shared__ __attribute__((aligned(16))) float fwd_dyn[];
-    [[maybe_unused]] constexpr int stamp_id = 1;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, i = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // provably wave-uniform: LDS-DMA bases stay scalar
     const AttnBlock ab_ = attn_block((int)((S + 64 * QB - 1) / (64 * QB)), (int)nh);
     const int64_t seq = ab_.seq, h = ab_.h, q0 = ab_.blk * (64 * QB);
     const int64_t H = nh * 64, ld = 3 * H;
     const __bf16* base = qkv + seq * S * ld;
-    MR_ASTAMP_WG(0);
 
     // K / V of this (sequence, head): rows beyond S are beyond the descriptors' extent (zero fill); the tile advance is a scalar offset
     const __bf16* Kg = base + H + h * 64;
@@ -401,9 +364,7 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_fwd_kernel(const __bf16
             mode = tile_mode(wq_uniform, wq_code, __builtin_amdgcn_readfirstlane(Ku[t]));
             if (wq_allpad && (int64_t)(t + 1) * TK <= S) mode = TILE_UNIFORM;
         }
-        MR_ASTAMP(0);
         if (t + 1 < nt) stage(t + 1, b ^ 1);      // next tile: straight into the other buffer (last read one iteration ago, behind that iteration's barrier)
-        MR_ASTAMP(1);
         if (!MASKED || mode != TILE_SKIP) {
         bf16x8 pf[QB][2];
         constexpr bool V_EARLY = !MASKED;
@@ -425,7 +386,6 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_fwd_kernel(const __bf16
                 st[qb][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf[qb][1], a, 0, 0, 0);
             }
         }
-        MR_ASTAMP(2);
         // the V fragments do not depend on the softmax: the first half (keys 0-31) is requested now and lands while it runs; the
         // second half after it (its registers are the softmax's), landing under the first half's MFMAs
         // (the masked variant holds the codes as well and would lose its third wave per SIMD to these 16 registers: it asks late)
@@ -488,7 +448,6 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_fwd_kernel(const __bf16
             pf[qb][1] = pack_acc_pair(st[qb][2], st[qb][3]);
         }
         }
-        MR_ASTAMP(3);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!V_EARLY) {
 #pragma unroll
@@ -513,12 +472,9 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_fwd_kernel(const __bf16
                     ot[qb][db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qb][t2], ot[qb][db], 0, 0, 0);
             }
         }
-        MR_ASTAMP(4);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this wave's pieces of tile t + 1 have landed
-        MR_ASTAMP(5);
         __syncthreads();
-        MR_ASTAMP(6);
     }
     // lane holds O^T[d = 16 db + 4 g + r][query i]: 4 consecutive d of one row -> one 8-byte store per (qb, db)
 #pragma unroll
@@ -538,12 +494,11 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_fwd_kernel(const __bf16
             }
         }
     }
-    MR_ASTAMP_WG(1);
 }
 
 // ------------------------------------------------------------------------------------------------ dQ (+ delta = rowsum(dO * O))
 template <int QB, bool MASKED>
-__global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMASKED)) void attn_bwd_dq_kernel(const __bf16* __restrict__ qkv, const int32_t* __restrict__ code,
+__global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const __bf16* __restrict__ qkv, const int32_t* __restrict__ code,
                                                              const __bf16* __restrict__ o, const __bf16* __restrict__ dout,
                                                              const float* __restrict__ lse, float* __restrict__ delta,
                                                              __bf16* __restrict__ dqkv, const float* __restrict__ rot_tab,
@@ -552,10 +507,9 @@ __global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMA
     __shared__ __attribute__((aligned(16))) char Ks[2][TILE_B];       // LDS-DMA images: row reads (S^T) and tr reads (dQ^T)
     __shared__ __attribute__((aligned(16))) char Vs[2][TILE_B];       // row reads (dP^T)
     // the key codes, the per-key bias and the tile classes of the WHOLE sequence: written once, in the prologue, by all four waves (dynamic LDS: 8 bytes per
-    // padded position + 4 per tile).  Staged tile by tile by wave 0, their global loads parked that wave ~700 cycles at the top of every tile (stamps,
-    // scripts/attn_dq_stamps.py) and the other three waited for it at the barrier
+    // padded position + 4 per tile).  Staged tile by tile by wave 0, their global loads parked that wave ~700 cycles at the top of every tile (stamps)
+    // and the other three waited for it at the barrier
     extern __shared__ __attribute__((aligned(16))) float dq_dyn[];
-    [[maybe_unused]] constexpr int stamp_id = 2;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, i = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const AttnBlock ab_ = attn_block((int)((S + 64 * QB - 1) / (64 * QB)), (int)nh);
@@ -564,11 +518,10 @@ __global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMA
     const __bf16* base = qkv + seq * S * ld;
     const int32_t* code_seq = MASKED ? code + seq * S : nullptr;
     const float inv_S = 1.0f / (float)S;
-    MR_ASTAMP_WG(0);
     const int seq_rot0 = rot_tab != nullptr ? (int)((seq * S) % rot_rows) : 0;      // (uniform; once per workgroup)
     const bool rot_short = rot_rows < S;
 
-    // The prologue's requests, ALL in flight before anything waits (round 5, stamps: scripts/attn_dq_stamps.py): the first key tile's DMA, then this
+    // The prologue's requests, ALL in flight before anything waits (round 5, stamps): the first key tile's DMA, then this
     // lane's 12 fragment loads, its LSE and code -- from the row clamped into the sequence, the value discarded afterwards, because a load under `if (row < S)`
     // is a basic block of its own and the compiler waited for each block's three loads before issuing the next: five serial round trips.  Measured: the
     // dK / dV kernel's prologue 10.9 k -> 8.5 k cycles; this kernel's stays at 16.4 k of a first-round workgroup's 59 k -- it is bound by its BYTES (three
@@ -726,9 +679,7 @@ __global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMA
         const bool need_bias = mode == TILE_GENERAL;         // (masked kernels; the unmasked ones take nb_c)
         const bool skip = MASKED && mode == TILE_SKIP;       // stage, wait and synchronise only: every weight of the tile is 0 for this wave
         const int b = t & 1;
-        MR_ASTAMP(0);
         if (t + 1 < nt) stage(t + 1, b ^ 1);
-        MR_ASTAMP(1);
         if (!skip) {
         bf16x8 dsf[QB][2];
         // scores, P, dS of the tile (the first two products + the per-score arithmetic).  Masked kernels: instantiated twice under ONE wave-uniform
@@ -773,7 +724,6 @@ __global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMA
         } else {
             scores(nb_c);
         }
-        MR_ASTAMP(2);
         // K^T fragments (asm reads, explicit waits: see tr_frag_d_issue), one 32-key half at a time: the second half is requested once
         // the first half's MFMAs are issued and lands under them (its 16 registers are the first half's: 3 waves per SIMD)
 #pragma unroll
@@ -793,11 +743,8 @@ __global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMA
             }
         }
         }
-        MR_ASTAMP(3);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this wave's pieces of tile t + 1 have landed
-        MR_ASTAMP(4);
         __syncthreads();
-        MR_ASTAMP(5);
     };
     if constexpr (MASKED) {
         for (int t = 0; t < nt; ++t)
@@ -807,7 +754,6 @@ __global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMA
         if (ragged) tile_body(nt - 1, std::true_type{}, TILE_GENERAL);
         else tile_body(nt - 1, std::false_type{}, TILE_GENERAL);
     }
-    { const int t = 13; MR_ASTAMP(0); }
     f32x4 cs[4];
 #pragma unroll
     for (int db = 0; db < 4; ++db) cs[db] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -844,10 +790,8 @@ __global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMA
             }
         }
     }
-    { const int t = 13; MR_ASTAMP(1); }
     if (colsum != nullptr)        // wave-uniform: partial row (sequence, query block), columns of this head's q
         block_colsum_store(cs, red, colsum + (seq * ((S + 64 * QB - 1) / (64 * QB)) + ab_.blk) * ld + h * 64, tid);
-    MR_ASTAMP_WG(1);
 }
 
 // ------------------------------------------------------------------------------------------------ dK, dV
@@ -856,14 +800,14 @@ __global__ __launch_bounds__(256, (MASKED ? MR_ATTN_OCC_DQ : MR_ATTN_OCC_DQ_UNMA
 // Per query of the streamed tile the staging threads provide: -lse * log2 e (-inf beyond the sequence: p = 0), delta, the
 // code (CODE_PADQ for a row without allowed key) and, for such rows, the uniform weight 1/S.
 template <int KB, bool MASKED>
-__global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_bwd_dkv_kernel(const __bf16* __restrict__ qkv, const int32_t* __restrict__ code,
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const __bf16* __restrict__ qkv, const int32_t* __restrict__ code,
                                                               const __bf16* __restrict__ dout, const float* __restrict__ lse,
                                                               const float* __restrict__ delta, __bf16* __restrict__ dqkv,
                                                               const float* __restrict__ rot_tab, int64_t rot_rows,
                                                               float* __restrict__ colsum, int64_t S, int64_t nh, const int tile_modes) {
     __shared__ __attribute__((aligned(16))) float red[4][64];
     // A ring of THREE query tiles, requested TWO tiles ahead (round 5): with two buffers the wait for tile t + 1 at the end of tile t took ~900 of a tile's
-    // 4 300 cycles (stamps, scripts/attn_dkv_stamps.py) -- under the load of 512 resident workgroups an LDS-DMA request needs ~3 000 cycles to land, more
+    // 4 300 cycles (stamps) -- under the load of 512 resident workgroups an LDS-DMA request needs ~3 000 cycles to land, more
     // than a tile's arithmetic.  52 KiB per workgroup: two per CU, as the registers allow anyway.
     constexpr int NB = 3;
     __shared__ __attribute__((aligned(16))) char Qs[NB][TILE_B];       // LDS-DMA images: row reads (S) and tr reads (dK^T)
@@ -873,7 +817,6 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_bwd_dkv_kernel(const __
     // by wave 0, their global loads -- ~3 000 cycles under load -- were what the staging wave waited for at the end of every tile, and the other
     // three waited for it at the barrier: ~700 of a tile's 4 300 cycles (stamps).
     extern __shared__ __attribute__((aligned(16))) float dkv_dyn[];
-    [[maybe_unused]] constexpr int stamp_id = 3;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, i = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const AttnBlock ab_ = attn_block((int)((S + 64 * KB - 1) / (64 * KB)), (int)nh);
@@ -882,7 +825,6 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_bwd_dkv_kernel(const __
     const __bf16* base = qkv + seq * S * ld;
     const int32_t* code_seq = MASKED ? code + seq * S : nullptr;
     const float inv_S = 1.0f / (float)S;
-    MR_ASTAMP_WG(0);
     const int seq_rot0 = rot_tab != nullptr ? (int)((seq * S) % rot_rows) : 0;      // (uniform; once per workgroup)
     const bool rot_short = rot_rows < S;
 
@@ -1027,9 +969,7 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_bwd_dkv_kernel(const __
             mode = qc == CODE_DEAD ? (int)TILE_SKIP : tile_mode(wk_uniform, wk_code, qc);
         }
         const bool FAST = MASKED && mode == TILE_FAST;
-        MR_ASTAMP(0);
         if (t + 2 < nt) stage(t + 2, b2);
-        MR_ASTAMP(1);
         if (!MASKED || mode != TILE_SKIP) {
         const bool tile_pad = MASKED && !FAST && Fs[t] != 0;
 #pragma unroll
@@ -1121,22 +1061,18 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_bwd_dkv_kernel(const __
             }
         }
         }
-        MR_ASTAMP(2);
         if (t + 2 < nt) {
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");          // this wave's pieces of tile t + 1 have landed; the 4 of tile t + 2 stay in flight
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        MR_ASTAMP(3);
         // a RAW barrier: __syncthreads() carries a fence that the compiler lowers to s_waitcnt vmcnt(0) -- it would drain the requests of tile t + 2.
         // What the barrier must order is in LDS: this wave's reads of the slot tile t + 3 will overwrite (all retired: the asm reads were waited for,
         // the others feed arithmetic that has issued)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        MR_ASTAMP(4);
     }
-    { const int t = 13; MR_ASTAMP(0); }
     // lane holds dK^T / dV^T [d = 16 db + 4 g + r][key i].  dK: the 1/8 folded into kf was on the OTHER operand of S = q . (k/8), so
     // d(score)/dk = q / 8 still has to be applied here.  Both tiles leave as whole rows through the wave's share of the Q / dO buffers (free since the
     // loop's last barrier): store_rows_via_lds.
@@ -1165,14 +1101,12 @@ __global__ __launch_bounds__(256, MR_ATTN_OCC) void attn_bwd_dkv_kernel(const __
         store_rows_via_lds<KB>(&Qs[0][0] + wave * (KB * 2048), ok_, grow + H, ld, row0, S, lane);
         store_rows_via_lds<KB>(&Ds[0][0] + wave * (KB * 2048), ov_, grow + 2 * H, ld, row0, S, lane);
     }
-    { const int t = 13; MR_ASTAMP(1); }
     if (colsum != nullptr) {      // wave-uniform: partial row (sequence, key block), columns of this head's k and v
         float* prow = colsum + (seq * ((S + 64 * KB - 1) / (64 * KB)) + ab_.blk) * ld;
         block_colsum_store(csk, red, prow + H + h * 64, tid);
         __syncthreads();
         block_colsum_store(csv, red, prow + 2 * H + h * 64, tid);
     }
-    MR_ASTAMP_WG(1);
 }
 
 
@@ -1203,7 +1137,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd1_kernel(const __bf16* __restr
     __shared__ __attribute__((aligned(16))) float Ls[2][TK], Dl[2][TK], Us[2][TK];
     __shared__ __attribute__((aligned(16))) int32_t Cs[2][TK];
     __shared__ __attribute__((aligned(16))) float red[8][192];          // column-sum partials: [wave][q | k | v third][64]
-    [[maybe_unused]] constexpr int stamp_id = 4;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, i = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const AttnBlock ab_ = attn_block(1, (int)nh);
@@ -1212,7 +1145,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd1_kernel(const __bf16* __restr
     const __bf16* base = qkv + seq * S * ld;
     const int32_t* code_seq = MASKED ? code + seq * S : nullptr;
     const float inv_S = 1.0f / (float)S;
-    MR_ASTAMP_WG(0);
     const int seq_rot0 = rot_tab != nullptr ? (int)((seq * S) % rot_rows) : 0;      // (uniform; once per workgroup)
     const bool rot_short = rot_rows < S;
 
@@ -1306,7 +1238,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd1_kernel(const __bf16* __restr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // this wave's K / 8 fragments from the staged images (rows past the sequence are zeros there): the prologue of every workgroup of a round runs
-    // at once and is bound by the bytes it requests (~11 B / clk / CU: stamps, scripts/attn_bwd1_stamps.py); K came twice, 31 of its 117 KB
+    // at once and is bound by the bytes it requests (~11 B / clk / CU: stamps); K came twice, 31 of its 117 KB
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -1368,23 +1300,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd1_kernel(const __bf16* __restr
     };
 
     const int nt = (int)((S + TK - 1) / TK);
-#ifdef MR_ATTN_BWD1_PRIO
-    // experiment (MI355X_MICROARCH.md, "two waves per SIMD", item 4): the second-dispatched half of the workgroup is the arbitration loser of every
-    // segment; one static s_setprio 1 for it, no per-segment flips.  Same instructions, same results.  Measured (round 6, scripts/build_diag.sh prio attention
-    // -fno-slp-vectorize -DMR_ATTN_BWD1_PRIO, scripts/attn_bench.py, alternating on one box): base ViT 77.4-77.5 us against 76.3-77.1, large ViT 100.5-101.1 against
-    // 99.0-99.5, S = 130 58.8 against 56.8-57.3 -- 0.5-3 % SLOWER here (this kernel's halves are not in the compute / load alternation the guide measured): off.
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
     for (int t = 0; t < nt; ++t) {
         const int b = t & 1;
-        MR_ASTAMP(0);
         if (t + 1 < nt) {
             stage(t + 1, b ^ 1);
             side_issue((int64_t)(t + 1) * TK);
         }
-        MR_ASTAMP(1);
         if (t > 0) dq_tile(t - 1, b ^ 1);
-        MR_ASTAMP(2);
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
             // P and dS of this 32-query half, rounded to bf16 as soon as they exist (they are MFMA operands and the LDS payload as bf16
@@ -1466,17 +1388,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd1_kernel(const __bf16* __restr
                     dk[kb][db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt, dsf[kb], dk[kb][db], 0, 0, 0);
                 }
             }
-            MR_ASTAMP(3 + t2);
         }
         if (t + 1 < nt) { side_compute(); side_store(b ^ 1); }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // this wave's pieces of tile t + 1 have landed; its dS stores are out
-        MR_ASTAMP(5);
         __syncthreads();
-        MR_ASTAMP(6);
     }
-    { const int t = 13; MR_ASTAMP(0); }
     dq_tile(nt - 1, (nt - 1) & 1);
-    { const int t = 13; MR_ASTAMP(1); }
 
     // ---- dK / dV of this wave's 32 keys + the column sums of everything this workgroup stored ----
     // The lane holds [d = 16 db + 4 g + r][key i]: stored from there, a wave instruction wrote 16 rows x 32 bytes -- 16 partial lines -- and the 16 such
@@ -1517,7 +1434,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd1_kernel(const __bf16* __restr
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // the reads are done before the next part overwrites the region
     }
-    { const int t = 13; MR_ASTAMP(2); }
     if (colsum != nullptr) {      // wave-uniform: ONE partial row per sequence; this head's 64 columns of q, k, v
         float* prow = colsum + seq * ld;
         // k and v: every wave holds all 64 dims for its keys -> sum over the 16 lanes of a DPP row, then over the 8 waves; q: wave (qdb, qh) holds
@@ -1544,7 +1460,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd1_kernel(const __bf16* __restr
             prow[(tid >> 6) * H + h * 64 + (tid & 63)] = sum;
         }
     }
-    MR_ASTAMP_WG(1);
 }
 
 // ------------------------------------------------------------------------------------------------ dQ, dK, dV of a SHORT sequence (S <= 32): one WAVE per (sequence, head)
@@ -1791,12 +1706,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_small_kernel(const __bf16* __
     }
 }
 
-// MR_ATTN_QB_S (diagnostic): sequences longer than this use two query / key blocks per workgroup (default 64)
-static int64_t attn_qb_threshold() {
-    static int64_t v = -1;
-    if (v < 0) v = mr_env_int("MR_ATTN_QB_S", 64);
-    return v;
-}
+// sequences longer than this use two query / key blocks per workgroup
+constexpr int64_t QB_S = 64;
 
 template <int QB>
 static dim3 attn_grid(int64_t S, int64_t nh, int64_t nseq) {
@@ -1818,7 +1729,7 @@ extern "C" int mr_attention_fwd(const void* qkv, const int32_t* code, void* out,
     const int64_t ntp_ = (nt_ + 11) / 12 * 12;                            // (the kernels fill their tables in unconditional batches of 12 tiles)
     const size_t fwd_smem = (size_t)(ntp_ * TK * 8 + ntp_ * 4);             // key codes, bias and tile classes of a sequence (dynamic LDS)
     MR_CHECK_ARG(fwd_smem <= 100 * 1024, "mr_attention_fwd: S = %ld is beyond what one workgroup's LDS holds (S <= 12 700)", (long)S);
-    const bool two = S > attn_qb_threshold();        // short sequences (audio 31, span 16): one 16-query block per wave
+    const bool two = S > QB_S;        // short sequences (audio 31, span 16): one 16-query block per wave
     if (two && code) hipLaunchKernelGGL((attn_fwd_kernel<2, true>), attn_grid<2>(S, nh, nseq), dim3(256), fwd_smem, s, q, code, o, lse, S, nh, tm);
     else if (two) hipLaunchKernelGGL((attn_fwd_kernel<2, false>), attn_grid<2>(S, nh, nseq), dim3(256), fwd_smem, s, q, code, o, lse, S, nh, tm);
     else if (code) hipLaunchKernelGGL((attn_fwd_kernel<1, true>), attn_grid<1>(S, nh, nseq), dim3(256), fwd_smem, s, q, code, o, lse, S, nh, tm);
@@ -1839,7 +1750,7 @@ static bool attn_small(int64_t S) { return mr_opts().attn_onepass != 0 && S <= S
 
 extern "C" int64_t mr_attention_bwd_colsum_rows(int64_t nseq, int64_t S) {
     if (attn_small(S) || attn_onepass(S)) return nseq;                  // one partial row per sequence
-    const int64_t per = (S > attn_qb_threshold()) ? 128 : 64;          // queries (keys) per workgroup
+    const int64_t per = (S > QB_S) ? 128 : 64;          // queries (keys) per workgroup
     return nseq * ((S + per - 1) / per);
 }
 
@@ -1870,7 +1781,7 @@ extern "C" int mr_attention_bwd(const void* qkv, const int32_t* code, const void
         MR_CHECK_LAUNCH("mr_attention_bwd (one pass)");
         return MR_OK;
     }
-    const bool two = S > attn_qb_threshold();
+    const bool two = S > QB_S;
     const int tm = mr_opts().attn_tile_modes;
     // the dK / dV kernel keeps a sequence's per-query scalars in dynamic LDS: 16 B per padded position + 8 B per tile (beside 52 KiB of static tiles)
     const int64_t nt_ = (S + TK - 1) / TK;
@@ -1893,12 +1804,3 @@ extern "C" int mr_attention_bwd(const void* qkv, const int32_t* code, const void
     MR_CHECK_LAUNCH("mr_attention_bwd");
     return MR_OK;
 }
-
-#ifdef MR_ATTN_STAMPS
-extern "C" int mr_diag_attn_stamps(unsigned long long* host_out) {      // diagnostic build only
-    (void)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_attn_stamps), sizeof(unsigned long long) * 512 * 16 * 8);
-    unsigned long long z = 0;
-    (void)z;
-    return 0;
-}
-#endif

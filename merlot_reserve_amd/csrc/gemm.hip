@@ -12,13 +12,12 @@
 // weight or activation is ever materialised in HBM.
 // Epilogue: bias / "rotary" diagonal scale / activation in the MFMA layout, then the tile goes
 // through LDS so that residual / gelu' operands are read and C is written as 16-byte row segments.
-#include <stdlib.h>
+#include "gemm_plan.h"
 #include "mr_common.h"
-#include "mr_options.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int BM = SMALL_TILE, BN = SMALL_TILE, BK = SMALL_BK;
 constexpr int LDK = 72;    // K-contiguous tile  [128 rows][64 k + 8 pad]   (144-B rows)
 constexpr int LDT = 144;   // K-strided tile     [64 k][128 cols + 16 pad]  (288-B rows: 8 k-rows tile all 64 banks)
 constexpr int TILE_ELEMS = 128 * LDK;  // == 64 * LDT == 9216
@@ -278,7 +277,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const mr_gemm_args p,
 
 // Several small problems of ONE operand layout in one launch (the contrastive loss's six logits / d-query / d-key products, each a
 // 17-23 us latency chain of 12 k-tiles on one or two workgroups when launched alone): block -> (problem, tile), no split-K.
-constexpr int SMALL_MAXG = 8;
 struct SmallGroup {
     int count;
     int tile_start[SMALL_MAXG + 1];
@@ -318,7 +316,9 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splits, i
     }
 }
 
-void launch_splitk_reduce(const mr_gemm_args* a, int64_t splits, hipStream_t s) {
+}  // namespace
+
+void mr_gemm_splitk_reduce(const mr_gemm_args* a, int64_t splits, hipStream_t s) {
     const int64_t n4 = a->M * a->N / 4;
     int64_t blocks = (n4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
@@ -326,165 +326,31 @@ void launch_splitk_reduce(const mr_gemm_args* a, int64_t splits, hipStream_t s) 
                        (int)splits, a->M, a->N, static_cast<const __bf16*>(a->bias), a->C, a->ldc, (int)a->c_dtype);
 }
 
-}  // namespace
-
-// gemm256.hip
-bool mr_gemm256_eligible(const mr_gemm_args* a);
-int mr_gemm256_launch(const mr_gemm_args* a, hipStream_t s, void (*reduce)(const mr_gemm_args*, int64_t, hipStream_t));
-
-bool mr_gemm256_grouped(const mr_gemm_args* list, int count, hipStream_t s);
-// gemm3.hip
-bool mr_gemm3_eligible(const mr_gemm_args* a);
-int mr_gemm3_launch(const mr_gemm_args* a, hipStream_t s);
-bool mr_gemm3_tn_grouped(const mr_gemm_args* list, int count, hipStream_t s);
-// gemm5.hip
-bool mr_gemm5_wanted(const mr_gemm_args* a);
-int mr_gemm5_launch(const mr_gemm_args* a, hipStream_t s);
-
-static int use_gemm256() {
-    static int v = -1;
-    if (v < 0) v = mr_env_int("MR_GEMM_V1_ONLY", 0) ? 0 : 1;
-    return v && !g_mr_opt_v1_only;
+void mr_gemm_small_launch(const mr_gemm_args* a, int64_t tiles, int64_t tiles_n, int64_t splits, int64_t kt_per_split, hipStream_t s) {
+    dim3 grid((unsigned)tiles, (unsigned)splits), block(256);
+    if (!a->transA && !a->transB) hipLaunchKernelGGL((gemm_bf16_kernel<false, false>), grid, block, 0, s, *a, (int)tiles_n, (int)kt_per_split);
+    else if (!a->transA && a->transB) hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), grid, block, 0, s, *a, (int)tiles_n, (int)kt_per_split);
+    else if (a->transA && !a->transB) hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, block, 0, s, *a, (int)tiles_n, (int)kt_per_split);
+    else hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, block, 0, s, *a, (int)tiles_n, (int)kt_per_split);
 }
 
-extern "C" int mr_gemm(const mr_gemm_args* a, void* stream) {
-    MR_CHECK_ARG(a != nullptr, "mr_gemm: null args");
-    MR_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "mr_gemm: empty problem M=%ld N=%ld K=%ld", (long)a->M, (long)a->N, (long)a->K);
-    MR_CHECK_ARG(a->A && a->B && a->C, "mr_gemm: null operand");
-    MR_CHECK_ARG(a->lda % 8 == 0 && a->ldb % 8 == 0, "mr_gemm: lda/ldb must be multiples of 8 (got %ld, %ld)", (long)a->lda, (long)a->ldb);
-    // the contiguous dimension of each operand is consumed in 16-byte chunks: a ragged extent is allowed when the
-    // row is padded (with zeros, by the caller) up to the next multiple of 8 inside the leading dimension
-    MR_CHECK_ARG(((a->transA ? a->M : a->K) + 7) / 8 * 8 <= a->lda, "mr_gemm: A rows must be padded to a multiple of 8 elements");
-    MR_CHECK_ARG(((a->transB ? a->K : a->N) + 7) / 8 * 8 <= a->ldb, "mr_gemm: B rows must be padded to a multiple of 8 elements");
-    MR_CHECK_ARG(((uintptr_t)a->A % 16) == 0 && ((uintptr_t)a->B % 16) == 0 && ((uintptr_t)a->C % 16) == 0,
-                 "mr_gemm: operands must be 16-byte aligned");
-    if (a->c_dtype == MR_DT_BF16) {
-        MR_CHECK_ARG(a->N % 8 == 0 && a->ldc % 8 == 0, "mr_gemm: bf16 output needs N, ldc multiples of 8");
-        MR_CHECK_ARG(!a->residual || a->ldr % 8 == 0, "mr_gemm: ldr must be a multiple of 8");
-        MR_CHECK_ARG(!a->aux || a->ldaux % 8 == 0, "mr_gemm: ldaux must be a multiple of 8");
-    } else {
-        MR_CHECK_ARG(a->c_dtype == MR_DT_F32, "mr_gemm: bad c_dtype %d", a->c_dtype);
-        MR_CHECK_ARG(!a->residual && !a->aux && !a->c2 && a->act == MR_ACT_NONE && a->out_grp == 0,
-                     "mr_gemm: fp32 output supports bias only");
-    }
-    MR_CHECK_ARG(!a->rot_tab || a->rot_rows > 0, "mr_gemm: rot_rows must be > 0");
-    MR_CHECK_ARG(!a->colsum || (use_gemm256() && mr_gemm_colsum_supported(a) && a->ldcs >= a->N && ((uintptr_t)a->colsum % 16) == 0 && a->ldcs % 4 == 0),
-                 "mr_gemm: colsum is only produced by the 256-row kernel with the aux epilogue (ask mr_gemm_colsum_supported)");
-    mr_gemm_args with_ws;                    // the current handle's split-K workspace when the caller brings none
-    if (a->workspace == nullptr && mr_current_handle() != nullptr && mr_current_handle()->ws != nullptr) {
-        int dev_now = -1;                    // the workspace lives on the handle's device: never hand it to a launch on another one
-        (void)hipGetDevice(&dev_now);
-        MR_CHECK_ARG(dev_now == mr_current_handle()->device, "mr_gemm: the current handle was created for device %d, this thread launches on device %d",
-                     mr_current_handle()->device, dev_now);
-        with_ws = *a;
-        with_ws.workspace = mr_current_handle()->ws;
-        with_ws.workspace_bytes = mr_current_handle()->ws_bytes;
-        a = &with_ws;
-    }
-    if (use_gemm256() && mr_gemm5_wanted(a)) return mr_gemm5_launch(a, static_cast<hipStream_t>(stream));      // two workgroups per CU
-    if (use_gemm256() && mr_gemm3_eligible(a)) {
-        mr_gemm3_launch(a, static_cast<hipStream_t>(stream));
-        MR_CHECK_LAUNCH("mr_gemm (ping-pong kernel)");
-        return MR_OK;
-    }
-    if (use_gemm256() && mr_gemm256_eligible(a)) {
-        mr_gemm256_launch(a, static_cast<hipStream_t>(stream), launch_splitk_reduce);
-        MR_CHECK_LAUNCH("mr_gemm (256-row kernel)");
-        return MR_OK;
-    }
-    const int64_t tm = (a->M + BM - 1) / BM, tn = (a->N + BN - 1) / BN;
-    MR_CHECK_ARG(tm * tn < (1LL << 30), "mr_gemm: grid too large");
-    // split-K: problems with few output tiles and a long contraction (every wgrad) cannot fill 256 CUs otherwise
-    const int64_t nk = (a->K + BK - 1) / BK;
-    int64_t splits = 1;
-    const bool plain = !a->rot_tab && !a->c2 && a->act == MR_ACT_NONE && !a->residual && !a->aux && a->out_grp == 0;
-    if (a->workspace && plain && a->N % 4 == 0 && tm * tn < 384 && nk >= 16) {
-        splits = (768 + tm * tn - 1) / (tm * tn);
-        if (splits > nk / 8) splits = nk / 8;
-        if (splits > 32) splits = 32;
-        const int64_t fit = a->workspace_bytes / (a->M * a->N * (int64_t)sizeof(float));
-        if (splits > fit) splits = fit;
-        if (splits < 2) splits = 1;
-    }
-    int64_t kt_per_split = (nk + splits - 1) / splits;
-    splits = (nk + kt_per_split - 1) / kt_per_split;
-    dim3 grid((unsigned)(tm * tn), (unsigned)splits), block(256);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!a->transA && !a->transB) hipLaunchKernelGGL((gemm_bf16_kernel<false, false>), grid, block, 0, s, *a, (int)tn, (int)kt_per_split);
-    else if (!a->transA && a->transB) hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), grid, block, 0, s, *a, (int)tn, (int)kt_per_split);
-    else if (a->transA && !a->transB) hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, block, 0, s, *a, (int)tn, (int)kt_per_split);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, block, 0, s, *a, (int)tn, (int)kt_per_split);
-    if (splits > 1) launch_splitk_reduce(a, splits, s);
-    mr_note_route("gemm_bf16_kernel<%d,%d>%s", (int)a->transA, (int)a->transB, splits > 1 ? " + splitk_reduce" : "");
-    MR_CHECK_LAUNCH("mr_gemm");
-    return MR_OK;
-}
-
-extern "C" int mr_gemm_grouped(const mr_gemm_args* list, int32_t count, void* stream) {
-    MR_CHECK_ARG(list != nullptr && count >= 1, "mr_gemm_grouped: empty list");
-    for (int k = 0; k < count; ++k) {          // the same operand checks mr_gemm makes, BEFORE any kernel sees the list (16-byte LDS-DMA loads / b128 stores)
+void mr_gemm_small_grouped_launch(const mr_gemm_args* list, int count, int64_t tiles, hipStream_t s) {
+    SmallGroup sg;
+    int64_t t = 0;
+    for (int k = 0; k < count; ++k) {
         const mr_gemm_args* a = &list[k];
-        MR_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "mr_gemm_grouped: problem %d is empty (M=%ld N=%ld K=%ld)", k, (long)a->M, (long)a->N, (long)a->K);
-        MR_CHECK_ARG(a->A && a->B && a->C, "mr_gemm_grouped: problem %d has a null operand", k);
-        MR_CHECK_ARG(a->lda % 8 == 0 && a->ldb % 8 == 0, "mr_gemm_grouped: problem %d: lda / ldb must be multiples of 8", k);
-        MR_CHECK_ARG(((uintptr_t)a->A % 16) == 0 && ((uintptr_t)a->B % 16) == 0 && ((uintptr_t)a->C % 16) == 0,
-                     "mr_gemm_grouped: problem %d: operands must be 16-byte aligned", k);
-        MR_CHECK_ARG(a->c_dtype != MR_DT_BF16 || (a->N % 8 == 0 && a->ldc % 8 == 0), "mr_gemm_grouped: problem %d: bf16 output needs N, ldc multiples of 8", k);
+        const int64_t tn = (a->N + BN - 1) / BN;
+        sg.tile_start[k] = (int)t;
+        sg.tiles_n[k] = (int)tn;
+        sg.p[k] = *a;
+        t += ((a->M + BM - 1) / BM) * tn;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (use_gemm256() && count <= 20 && mr_gemm3_tn_grouped(list, count, s)) {      // weight gradients: the TN ping-pong kernel
-        MR_CHECK_LAUNCH("mr_gemm_grouped (ping-pong kernel)");
-        return MR_OK;
-    }
-    // small problems of one layout (none of which the big kernels would take): ONE launch of the 128 x 128 kernel over all their tiles
-    if (count > 1 && count <= SMALL_MAXG) {
-        bool small = true;
-        int64_t tiles = 0;
-        SmallGroup sg;
-        for (int k = 0; small && k < count; ++k) {
-            const mr_gemm_args* a = &list[k];
-            small = a->transA == list[0].transA && a->transB == list[0].transB && !(use_gemm256() && (mr_gemm5_wanted(a) || mr_gemm3_eligible(a) || mr_gemm256_eligible(a)));
-            small = small && ((a->transA ? a->M : a->K) + 7) / 8 * 8 <= a->lda && ((a->transB ? a->K : a->N) + 7) / 8 * 8 <= a->ldb;
-            small = small && (a->c_dtype == MR_DT_BF16 || (a->c_dtype == MR_DT_F32 && !a->residual && !a->aux && !a->c2 && a->act == MR_ACT_NONE && a->out_grp == 0));
-            small = small && !a->colsum && (!a->rot_tab || a->rot_rows > 0);
-            small = small && (a->c_dtype != MR_DT_BF16 || ((!a->residual || a->ldr % 8 == 0) && (!a->aux || a->ldaux % 8 == 0)));
-            if (!small) break;
-            const int64_t tm = (a->M + BM - 1) / BM, tn = (a->N + BN - 1) / BN;
-            sg.tile_start[k] = (int)tiles;
-            sg.tiles_n[k] = (int)tn;
-            sg.p[k] = *a;
-            tiles += tm * tn;
-        }
-        if (small && tiles <= 4096) {
-            sg.count = count;
-            for (int k = count; k <= SMALL_MAXG; ++k) sg.tile_start[k] = (int)tiles;
-            dim3 grid((unsigned)tiles), block(256);
-            const bool ta = list[0].transA, tb = list[0].transB;
-            if (!ta && !tb) hipLaunchKernelGGL((gemm_bf16_grouped_kernel<false, false>), grid, block, 0, s, sg);
-            else if (!ta && tb) hipLaunchKernelGGL((gemm_bf16_grouped_kernel<false, true>), grid, block, 0, s, sg);
-            else if (ta && !tb) hipLaunchKernelGGL((gemm_bf16_grouped_kernel<true, false>), grid, block, 0, s, sg);
-            else hipLaunchKernelGGL((gemm_bf16_grouped_kernel<true, true>), grid, block, 0, s, sg);
-            mr_note_route("gemm_bf16_grouped_kernel<%d,%d> x%d", (int)ta, (int)tb, count);
-            MR_CHECK_LAUNCH("mr_gemm_grouped (small problems)");
-            return MR_OK;
-        }
-    }
-    if (count > 4) {        // the one-barrier kernel groups <= 4 problems per launch
-        for (int k = 0; k < count; k += 4) {
-            const int rc = mr_gemm_grouped(list + k, count - k < 4 ? count - k : 4, stream);
-            if (rc != MR_OK) return rc;
-        }
-        return MR_OK;
-    }
-    bool all_big = use_gemm256() && count > 1 && count <= 4;
-    for (int k = 0; all_big && k < count; ++k) all_big = list[k].M > 0 && list[k].N % 128 == 0;     // (256-wide tiles: N % 256, checked inside)
-    if (all_big && mr_gemm256_grouped(list, count, s)) {
-        MR_CHECK_LAUNCH("mr_gemm_grouped");
-        return MR_OK;
-    }
-    for (int k = 0; k < count; ++k) {          // not groupable: one launch per problem (identical results)
-        const int rc = mr_gemm(&list[k], stream);
-        if (rc != MR_OK) return rc;
-    }
-    return MR_OK;
+    sg.count = count;
+    for (int k = count; k <= SMALL_MAXG; ++k) sg.tile_start[k] = (int)tiles;
+    dim3 grid((unsigned)tiles), block(256);
+    const bool ta = list[0].transA, tb = list[0].transB;
+    if (!ta && !tb) hipLaunchKernelGGL((gemm_bf16_grouped_kernel<false, false>), grid, block, 0, s, sg);
+    else if (!ta && tb) hipLaunchKernelGGL((gemm_bf16_grouped_kernel<false, true>), grid, block, 0, s, sg);
+    else if (ta && !tb) hipLaunchKernelGGL((gemm_bf16_grouped_kernel<true, false>), grid, block, 0, s, sg);
+    else hipLaunchKernelGGL((gemm_bf16_grouped_kernel<true, true>), grid, block, 0, s, sg);
 }

@@ -8,7 +8,6 @@
 // Out-of-range rows / columns are fetched with an out-of-range buffer offset, which the hardware zero-fills.
 // Same contract and epilogue as gemm.hip (mr_gemm dispatches here for large problems).
 #include "gemm256_sched.h"
-#include "mr_options.h"
 
 namespace g256 {
 
@@ -81,7 +80,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
         (issued) = ia.valid;                                                                                            \
         if (ia.valid) {                                                                                                 \
             char* st_ = smem + ista * STAGE_A + wave * 4096;                                                            \
-            const unsigned sa = MR_DIAG_K(ia.kt0 + ika) * a_step;                                                       \
+            const unsigned sa = (unsigned)(ia.kt0 + ika) * a_step;                                                      \
             MR_DMA(ra, MR_LDS_PTR(void, st_), 16, ao0, sa, 0, 0);                                                       \
             MR_DMA(ra, MR_LDS_PTR(void, st_ + 1024), 16, ao1, sa, 0, 0);                                                \
             MR_DMA(ra, MR_LDS_PTR(void, st_ + 2048), 16, ao2, sa, 0, 0);                                                \
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
     do {                                                                                                                \
         if (ib.valid) {                                                                                                 \
             char* sb_ = smem + OFF_B + istb * STAGE_B + wave * (NBP * 1024);                                            \
-            const unsigned sb = MR_DIAG_K(ib.kt0 + ikb) * b_step;                                                       \
+            const unsigned sb = (unsigned)(ib.kt0 + ikb) * b_step;                                                      \
             MR_DMA(rb, MR_LDS_PTR(void, sb_), 16, bo0, sb, 0, 0);                                                       \
             MR_DMA(rb, MR_LDS_PTR(void, sb_ + 1024), 16, bo1, sb, 0, 0);                                                \
             if (NBP == 4) {                                                                                             \
@@ -124,10 +123,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
 
     if (ia.valid) { SET_OFFSETS_A(); SET_OFFSETS_B(); }
     int cw = bperm, csa = 0, csb = 0;
-#ifdef MR_DIAG_STAMPS
-    unsigned long long* stamps = static_cast<unsigned long long*>(ga.p[0].workspace);
-    int nstamp = 0;
-#endif
     Item ci = GET_ITEM(cw);
     if (!ci.valid) return;
     bool issued;
@@ -222,10 +217,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
                 bf16x8 bfr[JH];
                 if (h == 0) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) af[i] = MR_DIAG_FRAG((frag<TA, 256, BKT>(As, wm * 64 + i * 16, kk, lane)));
+                    for (int i = 0; i < 4; ++i) af[i] = frag<TA, 256, BKT>(As, wm * 64 + i * 16, kk, lane);
                 }
 #pragma unroll
-                for (int j = 0; j < JH; ++j) bfr[j] = MR_DIAG_FRAG((frag<!TB, BW, BKT>(Bs, wn * WCOLS + (h * JH + j) * 16, kk, lane)));
+                for (int j = 0; j < JH; ++j) bfr[j] = frag<!TB, BW, BKT>(Bs, wn * WCOLS + (h * JH + j) * 16, kk, lane);
                 // the DMA issue rides in the shadow of the fragment reads' latency / the previous unit's MFMAs
                 if (u == 0) ISSUE_B();
                 if (u == UNITS / 2) ISSUE_A(issued);
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < JH; ++j)
-                        MR_DIAG_MFMA(acc[i][h * JH + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][h * JH + j], 0, 0, 0));
+                        acc[i][h * JH + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][h * JH + j], 0, 0, 0);
             }
             int pre_now = 0;
             if constexpr (EARLY && PRE_ROW >= 0) {
@@ -262,7 +257,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
             csa = (csa == NSTAGE_A - 1) ? 0 : csa + 1;
             csb = (csb == NSTAGE_B - 1) ? 0 : csb + 1;
         };
-        MR_STAMP(0);
         {   // the first four k-tiles request the residual / aux row blocks (static register indices: peeled, not switched)
             const int nloop = ci.nkt - 1;
             if (nloop > 0) kstep(std::integral_constant<int, 0>{});
@@ -271,7 +265,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
             if (nloop > 3) kstep(std::integral_constant<int, 3>{});
             for (int t = 4; t < nloop; ++t) kstep(std::integral_constant<int, -1>{});
         }
-        MR_STAMP(1);
         {
             if (EARLY && epi_bf16) {
 #pragma unroll
@@ -301,7 +294,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
             kstep(std::integral_constant<int, -1>{});
         }
 
-        MR_STAMP(2);
         if (EARLY && epi_bf16) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) reg_fence(pbias[j]);
@@ -461,7 +453,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
                     const auto s0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane16_swap(ua[1], ub[1], false, false);
                     const int col = wcol0 + (2 * jp + (g & 1)) * 16 + (g >> 1) * 8;
-                    if (MR_DIAG_ST(mok && col < eN)) *reinterpret_cast<u32x4*>(rowp + col) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+                    if (mok && col < eN) *reinterpret_cast<u32x4*>(rowp + col) = u32x4{s0[0], s1[0], s0[1], s1[1]};
                 };
     #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -570,10 +562,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const G256Args ga) {
                 default: epilogue(std::integral_constant<int, 5>{}); break;
             }
         }
-        MR_STAMP(3);
-#ifdef MR_DIAG_STAMPS
-        ++nstamp;
-#endif
         cw += G;
         ci = GET_ITEM(cw);
     }
@@ -591,156 +579,10 @@ static void launch(const G256Args& ga, dim3 grid, hipStream_t s) {
 
 }  // namespace g256
 
-constexpr int64_t NUM_CU = 256;    // MI355X
-
-// Returns true when the problem suits the 256-row kernel (then *splits / tiling are filled in by mr_gemm256_launch).
-bool mr_gemm256_eligible(const mr_gemm_args* a) {
-    if (a->M < 512 || a->N < 96) return false;
-    if (a->residual && a->aux) return false;              // the epilogue prefetches ONE bf16 operand
-    if (!a->transA && a->K % 64 != 0) return false;       // K-contiguous operands are fetched in whole 128-B rows
-    if (a->transB && a->K % 64 != 0) return false;
-    const int64_t a_rows = a->transA ? a->K : a->M, b_rows = a->transB ? a->N : a->K;
-    if (a_rows * a->lda * 2 >= (1LL << 31) || b_rows * a->ldb * 2 >= (1LL << 31)) return false;   // 32-bit buffer offsets
-    return true;
-}
-
-extern "C" int64_t mr_gemm_colsum_rows(int64_t M) { return 4 * ((M + g256::BM - 1) / g256::BM); }
-extern "C" int32_t mr_gemm_colsum_supported(const mr_gemm_args* a) {
-    return a && mr_gemm256_eligible(a) && a->c_dtype == MR_DT_BF16 && a->aux && !a->residual && !a->c2 && a->act == MR_ACT_NONE &&
-           !a->rot_tab && a->out_grp == 0 && a->N % 4 == 0;
-}
-
-int mr_gemm256_launch(const mr_gemm_args* a, hipStream_t s, void (*reduce)(const mr_gemm_args*, int64_t, hipStream_t)) {
-    const int64_t tm = (a->M + g256::BM - 1) / g256::BM;
-    // tile width: the one that wastes the fewest CU-rounds (256 workgroups per round, one per CU)
-    int bn = 128;
-    static int force_bn = -1, grid_mode = -1, c256_cost = -1, c192_cost = -1;
-    if (force_bn < 0) force_bn = mr_env_int("MR_G256_BN", 0);
-    if (grid_mode < 0) grid_mode = mr_env_int("MR_G256_GRID", 0);
-    if (c256_cost < 0) c256_cost = mr_env_int("MR_G256_C256", 180);
-    if (c192_cost < 0) c192_cost = mr_env_int("MR_G256_C192", 150);
-    const bool can256 = a->N >= 256, can192 = a->N >= 192;
-    {
-        const int64_t t128 = tm * ((a->N + 127) / 128), t96 = tm * ((a->N + 95) / 96), t256 = tm * ((a->N + 255) / 256);
-        // measured: a 96-wide tile costs ~0.91 of a 128-wide one (the A side and the LDS-DMA issue do not shrink); a
-        // 256-wide one ~1.9 (twice the FLOPs for 4/3 of the LDS-DMA bytes, but its 2-stage ring drains behind every k-tile)
-        const int64_t c128 = ((t128 + 255) / 256) * 100, c96 = ((t96 + 255) / 256) * 91, c256 = ((t256 + 255) / 256) * c256_cost;
-        int64_t best = c128;
-        if (c96 < best && !a->rot_tab) { bn = 96; best = c96; }       // the prefetched "rotary" scales assume whole heads per wave
-        if (can256 && c256 < best) { bn = 256; best = c256; }
-        const int64_t t192 = tm * ((a->N + 191) / 192), c192 = ((t192 + 255) / 256) * c192_cost;
-        if (can192 && c192 < best) { bn = 192; best = c192; }
-    }
-    {
-        const int f = g_mr_opt_tile_n ? g_mr_opt_tile_n : force_bn;
-        if (f == 96 || f == 128 || (f == 256 && can256) || (f == 192 && can192)) bn = f;
-    }
-    if (a->rot_tab && bn == 96) bn = 128;
-    if (a->colsum && bn == 256 && can192) bn = 192;     // the column-sum accumulators beside a 256-wide tile's 128 accumulators spill (measured: +22 us)
-    const int64_t tn = (a->N + bn - 1) / bn;
-    const int64_t bk = g256::BK, full_grid = NUM_CU;
-    const int64_t nk = (a->K + bk - 1) / bk;
-    int64_t splits = 1;
-    const bool plain = !a->rot_tab && !a->c2 && a->act == MR_ACT_NONE && !a->residual && !a->aux && a->out_grp == 0;
-    if (a->workspace && plain && a->N % 4 == 0 && tm * tn < 192 && nk >= 16) {
-        splits = (512 + tm * tn - 1) / (tm * tn);
-        if (splits > nk / 6) splits = nk / 6;
-        if (splits > 64) splits = 64;
-        const int64_t fit = a->workspace_bytes / (a->M * a->N * (int64_t)sizeof(float));
-        if (splits > fit) splits = fit;
-        if (splits < 2) splits = 1;
-    }
-    int64_t kps = (nk + splits - 1) / splits;
-    splits = (nk + kps - 1) / kps;
-    const int64_t nwork = tm * tn * splits;
-    int64_t gsz = nwork < full_grid ? nwork : full_grid;         // persistent: one workgroup per CU (two with 4 waves)
-    if (grid_mode == 1) gsz = nwork;                             // (experiment) one item per workgroup
-    else if (grid_mode > 1) gsz = nwork < grid_mode ? nwork : grid_mode;
-    dim3 grid((unsigned)gsz);
-    g256::G256Args ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.count = 1; ga.nwork = (int)nwork; ga.splits = (int)splits; ga.kt_per_split = (int)kps;
-    static int xmode_env = -1;
-    if (xmode_env < 0) xmode_env = mr_env_int("MR_G256_XMODE", 1);
-    if (xmode_env && splits == 1 && gsz == full_grid && nwork >= 2 * full_grid) {
-        // choose the XCD partition: fewest rounds first (the slowest XCD sets the time), then least traffic out of L2
-        const double a_bytes = 2.0 * a->M * a->K, b_bytes = 2.0 * a->N * a->K;
-        double best = 1e300;
-        for (int px = 1; px <= 8; px *= 2) {
-            const int py = 8 / px;
-            if (px > tm || py > tn) continue;
-            if (mr_opts().xpx > 0 && px != mr_opts().xpx) continue;
-            int64_t rounds = 0;
-            for (int xi = 0; xi < px; ++xi)
-                for (int xj = 0; xj < py; ++xj) {
-                    const int64_t hm = (xi + 1) * tm / px - xi * tm / px, hn = (xj + 1) * tn / py - xj * tn / py;
-                    const int64_t r = (hm * hn + full_grid / 8 - 1) / (full_grid / 8);
-                    if (r > rounds) rounds = r;
-                }
-            const bool b_fits = b_bytes / py < 2.5e6;         // a cell's B slice stays in the XCD's 4-MiB L2
-            const double traffic = a_bytes * py + b_bytes * px * (b_fits ? 1.0 : (double)rounds);
-            const double cost = (double)rounds * 1e12 + traffic;
-            if (cost < best) { best = cost; ga.px = px; ga.py = py; }
-        }
-        if (best < 1e300) {
-            ga.xmode = 1; ga.tm = (int)tm; ga.tn = (int)tn; ga.xpanel = mr_opts().xpanel;
-        }
-    }
-    ga.tiles_n[0] = (int)tn;
-    ga.tile_start[0] = 0;
-    for (int k = 1; k <= g256::MAXG; ++k) ga.tile_start[k] = 0x7fffffff;
-    ga.p[0] = *a;
+void mr_gemm256_launch(const g256::G256Args& ga, int bn, int64_t grid_size, hipStream_t s) {
+    const dim3 grid((unsigned)grid_size);
     if (bn == 256) g256::launch<256>(ga, grid, s);
     else if (bn == 192) g256::launch<192>(ga, grid, s);
     else if (bn == 128) g256::launch<128>(ga, grid, s);
     else g256::launch<96>(ga, grid, s);
-    if (splits > 1) reduce(a, splits, s);
-    mr_note_route("g256::gemm256_kernel<%d,%d,%d>%s", bn, (int)a->transA, (int)a->transB, splits > 1 ? " + splitk_reduce" : "");
-    return 0;
-}
-
-// Grouped launch: count <= 4 problems with identical transA/transB, each eligible for the 256-row kernel, epilogue
-// limited to bias; 128-wide tiles, no split-K.  Returns false if the group does not qualify (caller falls back).
-bool mr_gemm256_grouped(const mr_gemm_args* list, int count, hipStream_t s) {
-    if (count < 1 || count > g256::MAXG) return false;
-    for (int k = 0; k < count; ++k) {
-        const mr_gemm_args* a = &list[k];
-        if (!mr_gemm256_eligible(a) || a->transA != list[0].transA || a->transB != list[0].transB) return false;
-        if (a->rot_tab || a->c2 || a->act != MR_ACT_NONE || a->residual || a->aux || a->out_grp != 0) return false;
-    }
-    // tile width for the whole group: fewest CU-rounds, a 256-wide tile costing ~1.8 of a 128-wide one (the large model's
-    // four weight gradients are 384 tiles of 128 = 1.5 rounds -> 2, but 192 tiles of 256 = one round)
-    static int c256_cost = -1;
-    if (c256_cost < 0) c256_cost = mr_env_int("MR_G256_GROUP_C256", 180);
-    int64_t t128 = 0, t256 = 0;
-    bool can256 = true;
-    for (int k = 0; k < count; ++k) {
-        const int64_t tm = (list[k].M + g256::BM - 1) / g256::BM;
-        t128 += tm * ((list[k].N + 127) / 128);
-        t256 += tm * ((list[k].N + 255) / 256);
-        can256 = can256 && list[k].N % 256 == 0;
-    }
-    int bn = (can256 && ((t256 + NUM_CU - 1) / NUM_CU) * c256_cost < ((t128 + NUM_CU - 1) / NUM_CU) * 100) ? 256 : 128;
-    if (g_mr_opt_group_tile_n == 128 || (g_mr_opt_group_tile_n == 256 && can256)) bn = g_mr_opt_group_tile_n;       // a forced width (tests, A/B)
-    g256::G256Args ga;
-    memset(&ga, 0, sizeof(ga));
-    int64_t tiles = 0;
-    for (int k = 0; k <= g256::MAXG; ++k) ga.tile_start[k] = 0x7fffffff;
-    int64_t nk_max = 0;
-    for (int k = 0; k < count; ++k) {
-        const mr_gemm_args* a = &list[k];
-        const int64_t tm = (a->M + g256::BM - 1) / g256::BM, tn = (a->N + bn - 1) / bn;
-        ga.tiles_n[k] = (int)tn;
-        ga.tile_start[k] = (int)tiles;
-        tiles += tm * tn;
-        ga.p[k] = *a;
-        const int64_t nk = (a->K + g256::BK - 1) / g256::BK;
-        if (nk > nk_max) nk_max = nk;
-    }
-    ga.count = count; ga.nwork = (int)tiles; ga.splits = 1; ga.kt_per_split = (int)nk_max;
-    dim3 grid((unsigned)(tiles < NUM_CU ? tiles : NUM_CU));
-    if (bn == 256) g256::launch<256>(ga, grid, s);
-    else g256::launch<128>(ga, grid, s);
-    mr_note_route("g256::gemm256_kernel<%d,%d,%d> grouped x%d", bn, (int)list[0].transA, (int)list[0].transB, count);
-    return true;
 }

@@ -4,48 +4,13 @@
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
+#include "gemm_plan.h"
 #include "mr_common.h"
 
-#ifdef MR_DIAG_SAMEK
-#define MR_DIAG_K(k) 0u     /* timing-only build: wrong results */
-#else
-#define MR_DIAG_K(k) (unsigned)(k)
-#endif
-
-#if defined(MR_DIAG_NOFRAG) || defined(MR_DIAG_NOMFMA)   /* timing-only builds: no LDS fragment reads */
-#define MR_DIAG_FRAG(x) bf16x8{}
-#else
-#define MR_DIAG_FRAG(x) (x)
-#endif
-#ifdef MR_DIAG_NOMFMA
-#define MR_DIAG_MFMA(x) do {} while (0)
-#else
-#define MR_DIAG_MFMA(x) x
-#endif
-#ifdef MR_DIAG_NOLOAD      /* timing-only build (wrong results): no LDS-DMA at all, cursors still advance */
-#define MR_DMA(...) do {} while (0)
-#else
 #define MR_DMA(...) __builtin_amdgcn_raw_ptr_buffer_load_lds(__VA_ARGS__)
-#endif
-#ifdef MR_DIAG_NOSTORE     /* timing-only build (no output): the bf16 epilogue computes everything and stores nothing */
-#define MR_DIAG_ST(c) ((c) && ga.nwork < 0)
-#else
-#define MR_DIAG_ST(c) (c)
-#endif
-#ifdef MR_DIAG_STAMPS
-#define MR_STAMP(slot)                                                                              \
-    do {                                                                                            \
-        unsigned long long t_;                                                                      \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
-        if (tid == 0 && nstamp < 64) stamps[(blockIdx.x * 64 + nstamp) * 4 + (slot)] = t_;          \
-    } while (0)
-#else
-#define MR_STAMP(slot) do {} while (0)
-#endif
 
 namespace g256 {
 
-constexpr int BM = 256, BK = 64;
 // B is staged 128 wide (BN = 128 | 96: 48-KiB stages, 3-stage ring, two k-tiles ahead) or 256 wide (BN = 256: 64-KiB
 // stages, 2-stage ring, one k-tile ahead).  The k-loop is bound by the LDS-DMA fill rate of a CU (~60-70 GB/s measured
 // with the MFMAs compiled out), so the 256 x 256 tile -- 2/3 of the bytes per FLOP -- is the fast one wherever the
@@ -155,22 +120,6 @@ __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)
 struct Item {
     int pi, m0, n0, kt0, nkt, split;
     bool valid;
-};
-
-constexpr int MAXG = 4;
-// One launch = up to MAXG independent problems (same layouts and tile width) sharing the persistent grid: the four
-// weight gradients of a transformer layer fill the 256 CUs together, with no split-K traffic.
-struct G256Args {
-    int count, nwork, splits, kt_per_split;
-    // XCD-blocked tile order (xmode = 1; single problem, no split-K, grid = 256): the 8 XCDs own the cells of a px x py
-    // partition of the tile grid and walk their cell in panels of XPANEL tile columns, so that the 32 workgroups of an
-    // XCD -- which move through K in lockstep -- ask their L2 for few distinct operand strips at a time, and a cell's
-    // slice of B stays L2-resident while its A strips stream through.  (With the plain row-major order every XCD swept
-    // all of B once per round of 256 tiles: rocprofv3 FETCH_SIZE showed 6x the operand bytes leaving L2 per launch.)
-    int xmode, px, py, tm, tn;
-    int xpanel;            // tile columns per panel of a cell's walk (0 = XPANEL; option "gemm_xpanel", an experiment knob)
-    int tiles_n[MAXG], tile_start[MAXG + 1];
-    mr_gemm_args p[MAXG];
 };
 
 constexpr int XPANEL = 8;

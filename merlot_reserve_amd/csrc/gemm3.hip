@@ -17,8 +17,7 @@
 // every B piece (k-tile t+1, waited for at the END of its MFMA section: both groups read it after the closing barrier), group 1
 // every A piece (k-tile t+2, counted wait in its next memory section).
 // PH = 2: per k-tile and wave TWO phases: phase 0 reads B (8 | 6 ds_read_b128) + A0 (8) and multiplies A0 x B (32 | 24 MFMAs),
-// phase 1 reads A1 (8) and multiplies A1 x B; A0 / A1 = the wave's two 64-row halves.  (-DMR_G3_PH4: four phases of 16 | 8
-// MFMAs, quadrants (A0,B0) (A0,B1) (A1,B1) (A1,B0): twice the barriers per MFMA.)
+// phase 1 reads A1 (8) and multiplies A1 x B; A0 / A1 = the wave's two 64-row halves.
 // Operand rings, filled by LDS-DMA (buffer_load ... lds, 1 KiB per wave instruction, zero fill beyond the extents):
 //     A: 3 stages x 32 KiB, two k-tiles ahead (issued in phase 0);
 //     B: 2 stages x {32,24} KiB: k-tile t+2 overwrites k-tile t's stage in phase 1, after the B reads of k-tile t
@@ -32,7 +31,6 @@
 #include <string.h>
 #include <type_traits>
 #include "gemm256_sched.h"
-#include "mr_options.h"
 
 namespace g3 {
 
@@ -50,27 +48,6 @@ template <int BN> struct Geo3 {
 };
 static_assert(Geo3<256>::LDS_BYTES == 160 * 1024 && Geo3<192>::LDS_BYTES == 144 * 1024, "LDS budget");
 
-#ifdef MR_G3_NOSYNC_EPI
-constexpr bool EPI_SYNC = false;
-#else
-constexpr bool EPI_SYNC = true;
-#endif
-// cache policy bits of the epilogue stores (raw_buffer_store aux: 1 = sc0, 2 = nt, 16 = sc1): experiment knobs, default 0
-#ifndef MR_G3_AUX_C
-#define MR_G3_AUX_C 0
-#endif
-#ifndef MR_G3_AUX_C2
-#define MR_G3_AUX_C2 0
-#endif
-#ifndef MR_G3_NA0
-#define MR_G3_NA0 4
-#endif
-constexpr int NA0 = MR_G3_NA0;        // A pieces (of a wave's four per k-tile) issued in phase 0
-#ifdef MR_G3_PH4
-constexpr bool PH4 = true;
-#else
-constexpr bool PH4 = false;
-#endif
 
 // MODE (the epilogue, fixed per launch: one problem per launch):
 //   0: bias | 1: bias + "rotary" scales | 2: bias + GELU, gelu' copy to c2 | 3: + residual | 4: x aux (+ column sums)
@@ -109,9 +86,6 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
     auto item_m0 = [&](int q) -> int { return q < 64 ? __builtin_amdgcn_readlane(m0v, q) : -1; };
     auto item_n0 = [&](int q) -> int { return __builtin_amdgcn_readlane(n0v, q & 63); };
     if (item_m0(0) < 0) return;
-#ifdef MR_G3_STAGGER          // experiment (scripts/build_g3_variants.sh): odd workgroups start late, so that their epilogues' store bursts fall into the others' k-loops
-    if (blockIdx.x & 8) for (int i = 0; i < MR_G3_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
     const mr_gemm_args& p0 = ga.p[0];
     const int nkt = (int)(p0.K >> 6);
     const unsigned lda2 = (unsigned)p0.lda * 2u, ldb2 = (unsigned)p0.ldb * 2u;
@@ -155,8 +129,7 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
             }                                                                                                           \
         }                                                                                                               \
     } while (0)
-    // the wave's four A pieces of a k-tile (rows 0-127: two, rows 128-255: two); the first NA0 are issued in phase 0, the rest lead
-    // phase 1's B pieces, so that the two phases' issue work (LDS reads + DMA) is balanced: 16 + NA0 against 8 + (8 - NA0) instructions
+    // the wave's four A pieces of a k-tile (rows 0-127: two, rows 128-255: two)
 #define G3_ISSUE_A_LO()                                                                                                 \
     do {                                                                                                                \
         issued = va;                                                                                                    \
@@ -275,26 +248,6 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
         }
     };
     fetch_bias(cn0);
-#ifdef MR_G3_STAMPS
-    unsigned long long* stamps = static_cast<unsigned long long*>(ga.p[0].workspace);
-    int nstamp = 0;
-#define G3_STAMP(slot)                                                                              \
-    do {                                                                                            \
-        unsigned long long t_;                                                                      \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
-        if (lane == 0 && (wave & 3) == 0 && nstamp < 8) stamps[((blockIdx.x * 2 + wr) * 8 + nstamp) * 4 + (slot)] = t_;  \
-    } while (0)
-    // per-k-tile stamps of the first 8 workgroups' wave 0 (second KiB-aligned region of the workspace)
-#define G3_KSTAMP(t)                                                                                \
-    do {                                                                                            \
-        unsigned long long t_;                                                                      \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                  \
-        if (lane == 0 && wave == 0 && blockIdx.x < 8 && nstamp < 4 && (t) < 16) stamps[65536 + (blockIdx.x * 4 + nstamp) * 16 + (t)] = t_;  \
-    } while (0)
-#else
-#define G3_STAMP(slot) do {} while (0)
-#define G3_KSTAMP(t) do {} while (0)
-#endif
     while (cm0 >= 0) {
         // accumulators TRANSPOSED (mfma(B-frag, A-frag)): the lane holds C[m = .. + li][n = .. + 4 g + r]
         f32x4 acc[8][NJ];
@@ -303,7 +256,6 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[i][j] = binit[j];
 
-        G3_STAMP(0);
         auto ktile = [&](auto first_c) {
             constexpr bool FIRST = decltype(first_c)::value;       // the tile's first k-tile: the previous tile's stores are in flight
             const char* As = smem + csa * STAGE_A;
@@ -380,15 +332,14 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
                 __builtin_amdgcn_s_setprio(0);
                 if (wr == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // B of k-tile t+1 has landed behind the closing barrier
                 G3_BARRIER();
-            } else if constexpr (!PH4) {
+            } else {
                 // ---------------- phase 0: A0 x B.  The B reads are retired AHEAD of the barrier (phase 1 restages B) ----------------
                 read_b(0, NJ);
                 __builtin_amdgcn_sched_barrier(0);      // B before A: the counted wait below relies on the issue order
                 read_a(0);
                 __builtin_amdgcn_sched_barrier(0);
                 G3_ISSUE_A_LO();
-                if constexpr (NA0 >= 3) G3_ISSUE_A_PIECE(ar2, 16384);
-                if constexpr (NA0 >= 4) { G3_ISSUE_A_PIECE(ar3, 16384 + 1024); G3_ADVANCE_A(); }
+                G3_ISSUE_A_HI();
                 G3_LGKM(8);
                 G3_BARRIER();
                 G3_LGKM(0);
@@ -397,8 +348,6 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
                 // ---------------- phase 1: A1 x B.  The A reads are retired ahead of the barrier (the next phase 0 restages A) ----------------
                 read_a(1);
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (NA0 < 3) G3_ISSUE_A_PIECE(ar2, 16384);
-                if constexpr (NA0 < 4) { G3_ISSUE_A_PIECE(ar3, 16384 + 1024); G3_ADVANCE_A(); }
                 G3_ISSUE_B_LO();
                 G3_ISSUE_B_HI();
                 G3_LGKM(0);
@@ -406,73 +355,31 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
                 G3_BARRIER();
                 mfmas(1, 0, NJ);
                 G3_BARRIER();
-            } else {
-                // ---------------- four phases: (A0,B0) (A0,B1) (A1,B1) (A1,B0) ----------------
-                read_b(0, 2);
-                read_a(0);
-                __builtin_amdgcn_sched_barrier(0);
-                G3_ISSUE_A_LO();
-                G3_BARRIER();
-                G3_LGKM(0);
-                mfmas(0, 0, 2);
-                G3_BARRIER();
-                read_b(2, NJ);
-                __builtin_amdgcn_sched_barrier(0);
-                G3_ISSUE_A_HI();
-                G3_LGKM(0);             // ahead of the barrier: B is restaged from the next phase on
-                G3_BARRIER();
-                mfmas(0, 2, NJ);
-                G3_BARRIER();
-                read_a(1);
-                __builtin_amdgcn_sched_barrier(0);
-                G3_ISSUE_B_LO();
-                G3_BARRIER();
-                G3_LGKM(0);
-                mfmas(1, 2, NJ);
-                G3_BARRIER();
-                G3_ISSUE_B_HI();
-                tile_wait();
-                G3_BARRIER();
-                mfmas(1, 0, 2);
-                G3_BARRIER();
             }
             csa = (csa == NSTAGE_A - 1) ? 0 : csa + 1;
             csb = (csb == NSTAGE_B - 1) ? 0 : csb + 1;
         };
-        G3_KSTAMP(0);
         ktile(std::integral_constant<bool, true>{});
-        for (int t = 1; t < nkt; ++t) { G3_KSTAMP(t); ktile(std::integral_constant<bool, false>{}); }
-        G3_STAMP(1);
+        for (int t = 1; t < nkt; ++t) ktile(std::integral_constant<bool, false>{});
 
         // ---------------- epilogue (bf16 output; registers + ordinary loads, no LDS) ----------------
-        // With EPI_SYNC the two groups' epilogues run side by side (group 0 waits for group 1's last MFMAs, group 1 waits behind
-        // its epilogue for group 0's, which restores the one-barrier offset); without, they run one after the other.
-        if (EPI_SYNC && wr == 0) G3_BARRIER();
+        // The two groups' epilogues run side by side (group 0 waits for group 1's last MFMAs, group 1 waits behind its epilogue
+        // for group 0's, which restores the one-barrier offset).
+        if (wr == 0) G3_BARRIER();
         {
             const int wrow0 = cm0 + wr * 128, wcol0 = cn0 + wc * WCOLS;
             constexpr int MR_EPI_MI = 8;
 #define MR_EPI_ROW_FENCE() do {} while (0)
 #include "gemm3_epilogue.inc"
 #undef MR_EPI_ROW_FENCE
-#ifndef MR_G3_NOSTORE
             have_stores = true;
-#endif
         }
-        G3_STAMP(2);
-#ifdef MR_G3_STAMPS
-        ++nstamp;
-#endif
-        if (EPI_SYNC && wr == 1) G3_BARRIER();
+        if (wr == 1) G3_BARRIER();
         ++qc;
         cm0 = item_m0(qc);
         cn0 = item_n0(qc);
     }
     if (wr == 0) G3_BARRIER();          // pairs with group 1's last barrier
-#ifdef MR_DIAG_RELEASE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 }
 
 
@@ -483,10 +390,7 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
 // persistence (K = tokens is long: 93-241 k-tiles, the prologue and the plain bf16 epilogue are < 2 % of a tile), up to 20
 // problems per launch: the weight gradients of TWO transformer layers fill the chip without split-K (216 tiles for the base
 // model) where one layer's four are 108; FOUR layers of the large model are 768 tiles = three full rounds where one layer's 192
-// leave a quarter of the CUs idle.
-struct TNProb { const void* A; const void* B; void* C; int M, N, lda, ldb, ldc, pad; };
-constexpr int TN_MAXG = 20;
-struct TNArgs { int count, K; int tile_start[TN_MAXG + 1]; int tiles_n[TN_MAXG]; TNProb p[TN_MAXG]; };
+// leave a quarter of the CUs idle.  (TNArgs: gemm_plan.h)
 
 __global__ __launch_bounds__(512, 2) void gemm3_tn_kernel(const TNArgs ta) {
     constexpr int NJ = 4, STAGE = 64 * 512, NSTAGE_A = 3, NSTAGE_B = 2, OFF_B = NSTAGE_A * STAGE, WAITN = 8;
@@ -627,105 +531,8 @@ __global__ __launch_bounds__(512, 2) void gemm3_tn_kernel(const TNArgs ta) {
 
 }  // namespace g3
 
-constexpr int64_t NUM_CU3 = 256;    // MI355X
-bool mr_gemm4_takes(const mr_gemm_args* a);
-int mr_gemm4_launch(const mr_gemm_args* a, int bn, const g256::G256Args& ga, int64_t gsz, hipStream_t s);
-
-// The ping-pong kernel takes: NT operands (A [M,K], B [N,K], K % 64 == 0), bf16 output, at least one full round of 256-row tiles'
-// worth of work, and one of the epilogue combinations the step uses -- bias; bias + "rotary"; bias + GELU with the gelu' copy;
-// residual; aux (with or without column sums).
-// persistent workgroups = CUs a launch may fill (mr_set_option "gemm_cus": 256, or fewer -- a multiple of 8 -- while a collective
-// kernel holds CUs: a 256-workgroup grid would then run its last workgroups as a second round behind the others)
-static int64_t g3_ncu() { return (g_mr_opt_gemm_cus >= 64 && g_mr_opt_gemm_cus < NUM_CU3) ? (g_mr_opt_gemm_cus & ~7) : NUM_CU3; }
-
-bool mr_gemm3_eligible(const mr_gemm_args* a) {
-    static int env = -1;
-    if (env < 0) env = mr_env_int("MR_GEMM3", 1);
-    if (!env || !g_mr_opt_gemm3) return false;
-    if (a->transA || !a->transB || a->c_dtype != MR_DT_BF16) return false;
-    const bool forced = g_mr_opt_gemm3 == 256 || g_mr_opt_gemm3 == 192;      // tests: any shape the kernel can take
-    if (a->K % 64 != 0) return false;
-    if (!forced && (a->K < 128 || a->N < 192 || a->M < 1024)) return false;
-    if (a->M * a->lda * 2 >= (1LL << 31) || a->N * a->ldb * 2 >= (1LL << 31)) return false;    // 32-bit buffer offsets
-    {
-        const int64_t last = a->out_grp > 0 ? ((a->M - 1) / a->out_grp) * a->out_grp_stride + a->out_grp_off + (a->M - 1) % a->out_grp : a->M - 1;
-        if ((last * a->ldc + a->N) * 2 >= (1LL << 31)) return false;
-    }
-    const int n_extra = (a->rot_tab != nullptr) + (a->residual != nullptr) + (a->aux != nullptr) + (a->c2 != nullptr);
-    if (n_extra > 1) return false;
-    if ((a->c2 != nullptr) != (a->act == MR_ACT_GELU1702)) return false;
-    if (a->colsum && !a->aux) return false;
-    if (a->bias && (a->residual || a->aux)) return false;      // the bias rides in the accumulators of the bias modes only
-    // enough tiles to fill the chip (short-K problems with few tiles go to the split-K path of the one-barrier kernel)
-    const int64_t tm = (a->M + 255) / 256;
-    if (tm * ((a->N + 191) / 192) > 64 * g3_ncu()) return false;     // <= 64 items per workgroup (the kernel keeps them one per lane)
-    static int min_tiles = -1;
-    if (min_tiles < 0) min_tiles = mr_env_int("MR_G3_MIN_TILES", 128);
-    if (!forced && tm * ((a->N + 255) / 256) < min_tiles) return false;
-    return true;
-}
-
-int mr_gemm3_launch(const mr_gemm_args* a, hipStream_t s) {
-    const int64_t tm = (a->M + 255) / 256;
-    // tile width: fewest CU-rounds, a 192-wide tile costing 3/4 of a 256-wide one
-    const int64_t t256 = tm * ((a->N + 255) / 256), t192 = tm * ((a->N + 191) / 192);
-    const int64_t ncu = g3_ncu();
-    const int64_t c256 = ((t256 + ncu - 1) / ncu) * 100, c192 = ((t192 + ncu - 1) / ncu) * 78;
-    int bn = (c192 < c256) ? 192 : 256;
-    if (g_mr_opt_gemm3 == 256 || g_mr_opt_gemm3 == 192) bn = g_mr_opt_gemm3;
-    const int64_t tn = (a->N + bn - 1) / bn, nwork = tm * tn;
-    const int64_t gsz = nwork < ncu ? nwork : ncu;
-    g256::G256Args ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.count = 1; ga.nwork = (int)nwork; ga.splits = 1; ga.kt_per_split = (int)(a->K / 64);
-    if (gsz == ncu && nwork >= 2 * ncu) {
-        // XCD partition of the tile grid (see G256Args.xmode): fewest rounds first, then least traffic out of L2
-        const double a_bytes = 2.0 * a->M * a->K, b_bytes = 2.0 * a->N * a->K;
-        double best = 1e300;
-        for (int px = 1; px <= 8; px *= 2) {
-            const int py = 8 / px;
-            if (px > tm || py > tn) continue;
-            if (mr_opts().xpx > 0 && px != mr_opts().xpx) continue;
-            int64_t rounds = 0;
-            for (int xi = 0; xi < px; ++xi)
-                for (int xj = 0; xj < py; ++xj) {
-                    const int64_t hm = (xi + 1) * tm / px - xi * tm / px, hn = (xj + 1) * tn / py - xj * tn / py;
-                    const int64_t r = (hm * hn + ncu / 8 - 1) / (ncu / 8);
-                    if (r > rounds) rounds = r;
-                }
-            const bool b_fits = b_bytes / py < 2.5e6;
-            const double traffic = a_bytes * py + b_bytes * px * (b_fits ? 1.0 : (double)rounds);
-            const double cost = (double)rounds * 1e12 + traffic;
-            if (cost < best) { best = cost; ga.px = px; ga.py = py; }
-        }
-        if (best < 1e300) { ga.xmode = 1; ga.tm = (int)tm; ga.tn = (int)tn; ga.xpanel = mr_opts().xpanel; }
-    }
-    ga.tiles_n[0] = (int)tn;
-    ga.tile_start[0] = 0;
-    for (int k = 1; k <= g256::MAXG; ++k) ga.tile_start[k] = 0x7fffffff;
-    ga.p[0] = *a;
-    {   // the one-wave-per-SIMD kernel (gemm4.hip) shares this tile plan
-        static int g4_env = -1;
-        if (g4_env < 0) g4_env = mr_env_int("MR_GEMM4", 1);
-        const int g4 = g_mr_opt_gemm4 >= 0 ? g_mr_opt_gemm4 : g4_env;
-        // (not the 256-wide bias mode: 256 accumulators + the bias rows overflow the wave's 512 registers -- 183 spilled, reloads inside
-        // the k-loop, 299 vs 91 us -- so that combination stays on the ping-pong kernel and gemm4<256,0> is not instantiated)
-        if (g4 && mr_gemm4_takes(a) && !(bn == 256 && a->bias && !a->residual)) return mr_gemm4_launch(a, bn, ga, gsz, s);
-    }
-    dim3 grid((unsigned)gsz), block(512);
-    int mode = 0;
-    if (a->c2) mode = 2;
-    else if (a->rot_tab) mode = 1;
-    else if (a->residual) mode = 3;
-    else if (a->aux) mode = 4;
-    static int ph_env = -1;
-    if (ph_env < 0) ph_env = mr_env_int("MR_G3_PH", 0);
-    // one phase per k-tile (half the barriers: 2-7 % faster at K <= 4096) except where it measured slower: the 256-wide aux / column-sum
-    // epilogue (its prefetch registers + the one-phase schedule's spill: 94 vs 86 us on the fc1 dgrad) and very long k-loops, where B
-    // requested one phase ahead by ONE group lands later than the two-phase schedule's (8192^3: 745 vs 729 us)
-    const int ph_auto = ((mode == 4 && bn == 256) || a->K >= 8192) ? 2 : 1;
-    int ph = g_mr_opt_gemm3_ph ? g_mr_opt_gemm3_ph : ph_env ? ph_env : ph_auto;
-    if (mode == 4 && bn == 256) ph = 2;      // <256,4,1> is not built: 20 spilled registers with a reload inside the k-loop's MFMA block
+void mr_gemm3_launch(const g256::G256Args& ga, int bn, int mode, int ph, int64_t grid_size, hipStream_t s) {
+    dim3 grid((unsigned)grid_size), block(512);
 #define G3_LAUNCH(MODE)                                                                               \
     do {                                                                                              \
         if (ph == 1) {                                                                                \
@@ -744,39 +551,8 @@ int mr_gemm3_launch(const mr_gemm_args* a, hipStream_t s) {
         default: G3_LAUNCH(4); break;
     }
 #undef G3_LAUNCH
-    mr_note_route("g3::gemm3_kernel<%d,%d,%d>", bn, mode, ph);
-    return 0;
 }
 
-// Grouped weight gradients on the TN ping-pong kernel: <= 8 problems, all transA = 1 / transB = 0 with one K, bf16 outputs, no
-// epilogue.  Returns false when the group does not qualify (the caller falls back to the one-barrier kernel's grouped launch).
-bool mr_gemm3_tn_grouped(const mr_gemm_args* list, int count, hipStream_t s) {
-    static int env = -1;
-    if (env < 0) env = mr_env_int("MR_GEMM3_TN", 1);
-    if (!env || !g_mr_opt_gemm3 || count < 1 || count > g3::TN_MAXG) return false;
-    if (g_mr_opt_group_tile_n != 0) return false;   // an explicitly requested tile width of the one-barrier kernel
-    g3::TNArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    int64_t tiles = 0;
-    for (int k = 0; k < count; ++k) {
-        const mr_gemm_args* a = &list[k];
-        if (!a->transA || a->transB || a->c_dtype != MR_DT_BF16 || a->K != list[0].K) return false;
-        if (a->bias || a->rot_tab || a->c2 || a->act != MR_ACT_NONE || a->residual || a->aux || a->out_grp != 0 || a->colsum) return false;
-        if (a->M % 8 || a->N % 8 || a->lda % 8 || a->ldb % 8 || a->ldc % 8) return false;
-        if (a->K * a->lda * 2 >= (1LL << 31) || a->K * a->ldb * 2 >= (1LL << 31) || a->M * a->ldc * 2 >= (1LL << 31)) return false;
-        const int64_t tm = (a->M + 255) / 256, tn = (a->N + 255) / 256;
-        ta.tile_start[k] = (int)tiles;
-        ta.tiles_n[k] = (int)tn;
-        tiles += tm * tn;
-        ta.p[k] = g3::TNProb{a->A, a->B, a->C, (int)a->M, (int)a->N, (int)a->lda, (int)a->ldb, (int)a->ldc, 0};
-    }
-    ta.tile_start[count] = (int)tiles;
-    ta.count = count;
-    ta.K = (int)list[0].K;
-    // worth it when the tiles fill most of the chip (one tile per workgroup, one workgroup per CU) and K is long
-    const bool forced = g_mr_opt_gemm3 == 256;
-    if (!forced && (tiles < 160 || tiles > 4 * NUM_CU3 || list[0].K < 2048)) return false;
+void mr_gemm3_tn_launch(const g3::TNArgs& ta, int64_t tiles, hipStream_t s) {
     hipLaunchKernelGGL(g3::gemm3_tn_kernel, dim3((unsigned)tiles), dim3(512), 0, s, ta);
-    mr_note_route("g3::gemm3_tn_kernel grouped x%d", count);
-    return true;
 }

@@ -78,18 +78,13 @@
     }
     // Stores widened to 16 B: lanes l and l+16 hold columns 4g..4g+3 of adjacent 16-column blocks; one v_permlane16_swap per
     // dword leaves every lane with 8 contiguous columns (lane rows g = 0/2 own block 2jp, columns 0-7 / 8-15; g = 1/3 block 2jp+1)
-    auto store_pair = [&](const __amdgpu_buffer_rsrc_t& r, unsigned rowoff, bool mok, int jp, bf16x4 va, bf16x4 vb, auto aux_c) {
-        constexpr int AUX = decltype(aux_c)::value;
+    auto store_pair = [&](const __amdgpu_buffer_rsrc_t& r, unsigned rowoff, bool mok, int jp, bf16x4 va, bf16x4 vb) {
         u32x2 ua = __builtin_bit_cast(u32x2, va), ub = __builtin_bit_cast(u32x2, vb);
         const auto s0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
         const auto s1 = __builtin_amdgcn_permlane16_swap(ua[1], ub[1], false, false);
         const int col = wcol0 + (2 * jp + (g & 1)) * 16 + (g >> 1) * 8;
         const unsigned off = (mok && col < eN) ? rowoff + (unsigned)col * 2u : OOB;
-#ifndef MR_G3_NOSTORE
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{s0[0], s1[0], s0[1], s1[1]}, r, off, 0, AUX);
-#else
-        asm volatile("" ::"v"(s0), "v"(s1), "v"(off));
-#endif
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{s0[0], s1[0], s0[1], s1[1]}, r, off, 0, 0);
     };
     // Full-line stores (round 6).  store_pair's wave instruction writes 16 rows x 64 B: half of a 128-byte line per row.  A CU's store path takes whole lines
     // 2-3 x faster (scripts/micro/store_bench.cpp: 16 CUs 24.6 against 11.2 B / clk / CU, one CU 44.7 against 14.4; all 256 at once 5.3 against 5.1 TB/s, the
@@ -106,8 +101,7 @@
 #undef MR_EPI_FULL_LINES
 #undef MR_EPI_FULL_LINES_DEFAULTED
 #endif
-    auto store_quad = [&](const __amdgpu_buffer_rsrc_t& r, int i_, int jq, bf16x4 a0, bf16x4 b0, bf16x4 a1, bf16x4 b1, auto aux_c) {
-        constexpr int AUX = decltype(aux_c)::value;
+    auto store_quad = [&](const __amdgpu_buffer_rsrc_t& r, int i_, int jq, bf16x4 a0, bf16x4 b0, bf16x4 a1, bf16x4 b1) {
         auto widen = [&](bf16x4 va, bf16x4 vb) -> u32x4 {
             const u32x2 ua = __builtin_bit_cast(u32x2, va), ub = __builtin_bit_cast(u32x2, vb);
             const auto s0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
@@ -125,12 +119,8 @@
         const int col = wcol0 + (2 * (2 * jq + (li >> 3)) + (g & 1)) * 16 + (g >> 1) * 8;
         const unsigned off1 = (gm1 < eM && col < eN) ? (unsigned)out_row(gm1) * (unsigned)e_ldc * 2u + (unsigned)col * 2u : OOB;
         const unsigned off2 = (gm2 < eM && col < eN) ? (unsigned)out_row(gm2) * (unsigned)e_ldc * 2u + (unsigned)col * 2u : OOB;
-#ifndef MR_G3_NOSTORE
-        __builtin_amdgcn_raw_buffer_store_b128(T1, r, off1, 0, AUX);
-        __builtin_amdgcn_raw_buffer_store_b128(T2, r, off2, 0, AUX);
-#else
-        asm volatile("" ::"v"(T1), "v"(T2), "v"(off1), "v"(off2));
-#endif
+        __builtin_amdgcn_raw_buffer_store_b128(T1, r, off1, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(T2, r, off2, 0, 0);
     };
 #pragma unroll
     for (int i = 0; i < MR_EPI_MI; ++i) {
@@ -183,25 +173,21 @@
         if constexpr (FULL_LINES) {
 #pragma unroll
             for (int jq = 0; jq < NJ / 4; ++jq) {
-                if constexpr (MODE == 2) store_quad(rc2, i, jq, od[4 * jq], od[4 * jq + 1], od[4 * jq + 2], od[4 * jq + 3], std::integral_constant<int, MR_G3_AUX_C2>{});
-                store_quad(rc, i, jq, oc[4 * jq], oc[4 * jq + 1], oc[4 * jq + 2], oc[4 * jq + 3], std::integral_constant<int, MR_G3_AUX_C>{});
+                if constexpr (MODE == 2) store_quad(rc2, i, jq, od[4 * jq], od[4 * jq + 1], od[4 * jq + 2], od[4 * jq + 3]);
+                store_quad(rc, i, jq, oc[4 * jq], oc[4 * jq + 1], oc[4 * jq + 2], oc[4 * jq + 3]);
             }
         } else {
 #pragma unroll
             for (int jp = 0; jp < NJ / 2; ++jp) {
-                if constexpr (MODE == 2) store_pair(rc2, rowoff, mok, jp, od[2 * jp], od[2 * jp + 1], std::integral_constant<int, MR_G3_AUX_C2>{});
-                store_pair(rc, rowoff, mok, jp, oc[2 * jp], oc[2 * jp + 1], std::integral_constant<int, MR_G3_AUX_C>{});
+                if constexpr (MODE == 2) store_pair(rc2, rowoff, mok, jp, od[2 * jp], od[2 * jp + 1]);
+                store_pair(rc, rowoff, mok, jp, oc[2 * jp], oc[2 * jp + 1]);
             }
         }
         if (NJ & 1) {                                          // BN = 192: the odd block keeps 8-byte stores
             const int col = wcol0 + (NJ - 1) * 16 + g * 4;
             const unsigned off = (mok && col < eN) ? rowoff + (unsigned)col * 2u : OOB;
-#ifndef MR_G3_NOSTORE
             if constexpr (MODE == 2) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, od[NJ - 1]), rc2, off, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, oc[NJ - 1]), rc, off, 0, 0);
-#else
-            asm volatile("" ::"v"(od[NJ - 1]), "v"(oc[NJ - 1]), "v"(off));
-#endif
         }
         if constexpr (CS) {
             // column sums of the stored tile per 64-row band (mr_gemm_args.colsum: partial row 4 * (m / 256) + (m % 256) / 64):

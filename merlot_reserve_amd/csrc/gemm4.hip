@@ -31,18 +31,10 @@
 #include <string.h>
 #include <type_traits>
 #include "gemm256_sched.h"
-#include "mr_options.h"
 
 namespace g4 {
 
 using namespace g256;
-
-#ifndef MR_G3_AUX_C
-#define MR_G3_AUX_C 0
-#endif
-#ifndef MR_G3_AUX_C2
-#define MR_G3_AUX_C2 0
-#endif
 
 template <int BN> struct Geo4 {
     static_assert(BN == 256 || BN == 192, "tile widths");
@@ -239,14 +231,12 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const G256Args ga) {
             // ---------------- half 0: k = 0..31 of the tile; reads k = 32..63; requests A(t+2) into the stage k-tile t-1 was read from ----------------
             half(std::integral_constant<int, 0>{}, As, Bs, std::true_type{}, std::integral_constant<int, 8>{});
             // k-tile t+1 has landed (every group issued before the newest 8 A pieces) and every read of k-tile t's stages is retired
-#ifndef MR_G4_NOSYNC        /* timing-only diagnostic build (wrong results): no wait, no barrier */
             if (FIRST && have_stores) wait_vmcnt<WAIT_FIRST>();
             else wait_vmcnt<8>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             G4_SB();
             __builtin_amdgcn_s_barrier();
             G4_SB();
-#endif
             // ---------------- half 1: k = 32..63; reads k-tile t+1's k = 0..31; requests B(t+2) into the stage k-tile t was read from ----------------
             half(std::integral_constant<int, 1>{}, An, Bn, std::false_type{}, std::integral_constant<int, PB>{});
             G4_ADVANCE();
@@ -263,9 +253,7 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const G256Args ga) {
 #include "gemm3_epilogue.inc"
 #undef MR_EPI_FULL_LINES
 #undef MR_EPI_ROW_FENCE
-#ifndef MR_G3_NOSTORE
             have_stores = true;
-#endif
         }
         ++qc;
         cm0 = item_m0(qc);
@@ -278,16 +266,11 @@ __global__ __launch_bounds__(256) void gemm4_kernel(const G256Args ga) {
 }  // namespace g4
 
 
-// Same eligibility and tile plan as the ping-pong kernel (mr_gemm3_eligible / the plan below mirrors mr_gemm3_launch): the caller
-// has checked mr_gemm3_eligible(a).
-// MODE 5 = plain product without bias (dgrads): mode 0's epilogue, and the tile's first multiply takes the MFMA's inline zero.
-bool mr_gemm4_takes(const mr_gemm_args* a) { return !a->c2 && !a->rot_tab && !a->aux; }
-
-// Same eligibility and tile plan as the ping-pong kernel: the caller (mr_gemm3_launch) has built `ga` and checked mr_gemm4_takes(a).
-int mr_gemm4_launch(const mr_gemm_args* a, int bn, const g256::G256Args& ga, int64_t gsz, hipStream_t s) {
-    const int mode = a->residual ? 3 : a->bias ? 0 : 5;
+// The ping-pong kernel's plan (gemm_route.cpp hands it over).  MODE 5 = plain product without bias (dgrads): mode 0's epilogue, and the tile's
+// first multiply takes the MFMA's inline zero.
+int mr_gemm4_launch(const g256::G256Args& ga, int bn, int mode, int64_t grid_size, hipStream_t s) {
     MR_CHECK_ARG(!(bn == 256 && mode == 0), "mr_gemm (gemm4): the 256-wide bias mode is not built (register budget); route it to the ping-pong kernel");
-    dim3 grid((unsigned)gsz), block(256);
+    dim3 grid((unsigned)grid_size), block(256);
 #define G4_LAUNCH(MODE)                                                                               \
     do {                                                                                              \
         if (bn == 256) hipLaunchKernelGGL((g4::gemm4_kernel<256, MODE>), grid, block, 0, s, ga);      \
@@ -299,7 +282,5 @@ int mr_gemm4_launch(const mr_gemm_args* a, int bn, const g256::G256Args& ga, int
         default: G4_LAUNCH(5); break;
     }
 #undef G4_LAUNCH
-    mr_note_route("g4::gemm4_kernel<%d,%d>", bn, mode);
-    MR_CHECK_LAUNCH("mr_gemm (gemm4)");
     return MR_OK;
 }

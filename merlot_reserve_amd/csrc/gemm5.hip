@@ -35,18 +35,10 @@
 #include <string.h>
 #include <type_traits>
 #include "gemm256_sched.h"
-#include "mr_options.h"
 
 namespace g5 {
 
 using namespace g256;
-
-#ifndef MR_G3_AUX_C
-#define MR_G3_AUX_C 0
-#endif
-#ifndef MR_G3_AUX_C2
-#define MR_G3_AUX_C2 0
-#endif
 
 constexpr int BN5 = 128;
 // NW = 4 waves.  (An eight-wave workgroup on 256 x 256 tiles under this k-loop -- the ping-pong kernel's geometry and operand traffic, BK = 32
@@ -148,26 +140,6 @@ __global__ __launch_bounds__(NW * 64, (Geo5<NW, TM, NS>::OCC)) void gemm5_kernel
         }                                                                                                               \
     } while (0)
 #define G5_SB() __builtin_amdgcn_sched_barrier(0)
-#ifdef MR_G5_STAMPS        /* diagnostic build: s_memtime at the start of a tile's k-loop, at its end and at the end of its epilogue -> workspace */
-#define G5_STAMP(slot)                                                                                         \
-    do {                                                                                                       \
-        unsigned long long t_;                                                                                 \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                             \
-        if (tid == 0 && qc < 8) static_cast<unsigned long long*>(p0.workspace)[(blockIdx.x * 8 + qc) * 4 + (slot)] = t_; \
-    } while (0)
-#else
-#define G5_STAMP(slot) do {} while (0)
-#endif
-#ifdef MR_G5_NOREAD        /* timing-only diagnostic builds (wrong results): scripts/build_g5_variants.sh */
-#define G5_RD(dst, ptr) asm volatile("" : "+v"(dst))
-#else
-#define G5_RD(dst, ptr) (dst) = *reinterpret_cast<const bf16x8*>(ptr)
-#endif
-#ifdef MR_G5_NOBAR
-#define G5_BARRIER() do {} while (0)
-#else
-#define G5_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
     int qc = 0, rs = 0;                 // rs: the stage the NEXT fragments are read from
     int cm0 = item_m0(0), cn0 = item_n0(0);
     bool have_stores = false;
@@ -246,8 +218,8 @@ __global__ __launch_bounds__(NW * 64, (Geo5<NW, TM, NS>::OCC)) void gemm5_kernel
                 acc[r][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[1][CUR], ar, acc[r][1], 0, 0, 0);
                 G5_SB();
                 if constexpr (!LAST) {               // the double-buffered fragments first: b0..b3, then (eight row blocks) row blocks 6, 7
-                    if (r < 4) G5_RD(b[r][NXT], rd + fb + r * 1024);
-                    else if (r < 6) G5_RD(a67[r - 4][NXT], rd + fa + (r + 2) * 1024);
+                    if (r < 4) b[r][NXT] = *reinterpret_cast<const bf16x8*>(rd + fb + r * 1024);
+                    else if (r < 6) a67[r - 4][NXT] = *reinterpret_cast<const bf16x8*>(rd + fa + (r + 2) * 1024);
                 }
                 if (r < PA) MR_DMA(ra_c, MR_LDS_PTR(void, st_ + wave * (PA * 1024) + r * 1024), 16, pao, so_ + r * pstep_a, 0, 0);
                 else if (r < ND) MR_DMA(rb_c, MR_LDS_PTR(void, st_ + STG_A + wave * (PB * 1024) + (r - PA) * 1024), 16, pbo, so_ + (r - PA) * pstep_b, 0, 0);
@@ -256,8 +228,8 @@ __global__ __launch_bounds__(NW * 64, (Geo5<NW, TM, NS>::OCC)) void gemm5_kernel
                 acc[r][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[3][CUR], ar, acc[r][3], 0, 0, 0);
                 G5_SB();
                 if constexpr (!LAST) {
-                    if (r < MIP) G5_RD(a[r < MIP ? r : 0], rd + fa + r * 1024);       // in place: this row block's MFMAs are issued
-                    else if (MI == 4) G5_RD(a67[(r - MIP) & 1][NXT], rd + fa + r * 1024);   // four row blocks: the double-buffered pair rides in these slots
+                    if (r < MIP) a[r < MIP ? r : 0] = *reinterpret_cast<const bf16x8*>(rd + fa + r * 1024);       // in place: this row block's MFMAs are issued
+                    else if (MI == 4) a67[(r - MIP) & 1][NXT] = *reinterpret_cast<const bf16x8*>(rd + fa + r * 1024);   // four row blocks: the double-buffered pair rides in these slots
                 }
                 G5_SB();
             }
@@ -265,12 +237,11 @@ __global__ __launch_bounds__(NW * 64, (Geo5<NW, TM, NS>::OCC)) void gemm5_kernel
             else wait_vmcnt<WAIT_RING>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             G5_SB();
-            G5_BARRIER();
+            __builtin_amdgcn_s_barrier();
             G5_SB();
             if constexpr (!LAST) rs = (rs == NSTG - 1) ? 0 : rs + 1;
             G5_ADVANCE();
         };
-        G5_STAMP(0);
         step(std::integral_constant<int, 0>{}, std::true_type{}, std::false_type{});
         for (int t = 1; t + 2 < nks; t += 2) {
             step(std::integral_constant<int, 1>{}, std::false_type{}, std::false_type{});
@@ -278,7 +249,6 @@ __global__ __launch_bounds__(NW * 64, (Geo5<NW, TM, NS>::OCC)) void gemm5_kernel
         }
         step(std::integral_constant<int, 1>{}, std::false_type{}, std::true_type{});          // (K % 64 == 0: an even number of steps >= 4)
 
-        G5_STAMP(1);
         // ---------------- epilogue (bf16 output; registers + ordinary loads, no LDS) ----------------
         {
             const int wrow0 = cm0 + wr * (TM / 2), wcol0 = cn0 + wc * WCOLS;
@@ -288,11 +258,8 @@ __global__ __launch_bounds__(NW * 64, (Geo5<NW, TM, NS>::OCC)) void gemm5_kernel
 #include "gemm3_epilogue.inc"
 #undef MR_EPI_FULL_LINES
 #undef MR_EPI_ROW_FENCE
-#ifndef MR_G3_NOSTORE
             have_stores = true;
-#endif
         }
-        G5_STAMP(2);
         ++qc;
         cm0 = item_m0(qc);
         cn0 = item_n0(qc);
@@ -314,100 +281,8 @@ __global__ __launch_bounds__(NW * 64, (Geo5<NW, TM, NS>::OCC)) void gemm5_kernel
 }  // namespace g5
 
 
-// Same operand / epilogue contract as the ping-pong kernel; mr_gemm asks this kernel FIRST (mr_gemm5_wanted -> mr_gemm5_takes checks the operand conditions itself).
-bool mr_gemm5_takes(const mr_gemm_args* a) {
-    if (a->transA || !a->transB || a->c_dtype != MR_DT_BF16 || a->K % 64 != 0 || a->K < 128) return false;
-    if (a->M * a->lda * 2 >= (1LL << 31) || a->N * a->ldb * 2 >= (1LL << 31)) return false;
-    {
-        const int64_t last = a->out_grp > 0 ? ((a->M - 1) / a->out_grp) * a->out_grp_stride + a->out_grp_off + (a->M - 1) % a->out_grp : a->M - 1;
-        if ((last * a->ldc + a->N) * 2 >= (1LL << 31)) return false;
-    }
-    const int n_extra = (a->rot_tab != nullptr) + (a->residual != nullptr) + (a->aux != nullptr) + (a->c2 != nullptr);
-    if (n_extra > 1) return false;
-    if ((a->c2 != nullptr) != (a->act == MR_ACT_GELU1702)) return false;
-    if (a->colsum && !a->aux) return false;
-    if (a->bias && (a->residual || a->aux)) return false;
-    const int64_t ncu = (g_mr_opt_gemm_cus >= 64 && g_mr_opt_gemm_cus < 256) ? (g_mr_opt_gemm_cus & ~7) : 256;
-    if (((a->M + 127) / 128) * ((a->N + 127) / 128) > 64 * 2 * ncu) return false;          // <= 64 items per workgroup (either tile height)
-    return true;
-}
-
-// Tile height of a problem: 128 x 128 tiles (deep ring, one workgroup per CU) where even the 128-row grid has no more tiles than the chip has
-// CUs, or on request (option "gemm5" = 3); 256 x 128 (two workgroups per CU) otherwise.
-static bool g5_rows128(const mr_gemm_args* a) {
-    const int v = mr_opts().gemm5;
-    if (v == 3) return true;
-    if (v == 1) return false;
-    static int env = -2;
-    if (env == -2) env = mr_env_int("MR_G5_ROWS128", -1);
-    if (env >= 0) return env != 0;
-    return ((a->M + 127) / 128) * ((a->N + 127) / 128) <= 256;
-}
-
-int mr_gemm5_launch(const mr_gemm_args* a, hipStream_t s) {
-    const int64_t ncu = (g_mr_opt_gemm_cus >= 64 && g_mr_opt_gemm_cus < 256) ? (g_mr_opt_gemm_cus & ~7) : 256;
-    const bool r128 = g5_rows128(a);                    // 128 x 128 tiles, deep ring, one workgroup per CU
-    const int64_t slots = r128 ? ncu : 2 * ncu;         // workgroups per CU
-    const int64_t bn = g5::BN5;
-    const int64_t tm = (a->M + (r128 ? 127 : 255)) / (r128 ? 128 : 256), tn = (a->N + bn - 1) / bn, nwork = tm * tn;
-    const int64_t gsz = nwork < slots ? nwork : slots;
-    g256::G256Args ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.count = 1; ga.nwork = (int)nwork; ga.splits = 1; ga.kt_per_split = (int)(a->K / 32);
-    if (gsz == slots && nwork >= 2 * slots) {
-        // XCD partition of the tile grid (see G256Args.xmode): fewest rounds first, then least traffic out of L2
-        const double a_bytes = 2.0 * a->M * a->K, b_bytes = 2.0 * a->N * a->K;
-        double best = 1e300;
-        for (int px = 1; px <= 8; px *= 2) {
-            const int py = 8 / px;
-            if (px > tm || py > tn) continue;
-            if (mr_opts().xpx > 0 && px != mr_opts().xpx) continue;
-            int64_t rounds = 0;
-            for (int xi = 0; xi < px; ++xi)
-                for (int xj = 0; xj < py; ++xj) {
-                    const int64_t hm = (xi + 1) * tm / px - xi * tm / px, hn = (xj + 1) * tn / py - xj * tn / py;
-                    const int64_t r = (hm * hn + slots / 8 - 1) / (slots / 8);
-                    if (r > rounds) rounds = r;
-                }
-            const bool b_fits = b_bytes / py < 2.5e6;
-            const double traffic = a_bytes * py + b_bytes * px * (b_fits ? 1.0 : (double)rounds);
-            const double cost = (double)rounds * 1e12 + traffic;
-            if (cost < best) { best = cost; ga.px = px; ga.py = py; }
-        }
-        if (best < 1e300) { ga.xmode = 1; ga.tm = (int)tm; ga.tn = (int)tn; ga.xpanel = mr_opts().xpanel; }
-    }
-    ga.tiles_n[0] = (int)tn;
-    ga.tile_start[0] = 0;
-    for (int k = 1; k <= g256::MAXG; ++k) ga.tile_start[k] = 0x7fffffff;
-    ga.p[0] = *a;
-    int mode = 5;
-    if (a->c2) mode = 2;
-    else if (a->rot_tab) mode = 1;
-    else if (a->residual) mode = 3;
-    else if (a->aux) mode = 4;
-    else if (a->bias) mode = 0;
-    static int st_env = -2, su_env = -2;
-    if (st_env == -2) st_env = mr_env_int("MR_G5_STAGGER", -1);
-    if (su_env == -2) su_env = mr_env_int("MR_G5_STAGGER_PCT", -1);
-    int st_mode = g_mr_opt_gemm5_stagger >= 0 ? g_mr_opt_gemm5_stagger : st_env >= 0 ? st_env : 1;
-    if (gsz <= ncu || r128) st_mode = 0;         // one workgroup per CU: nobody to be out of phase with (three per CU: no phase is set)
-    // ~ one k-loop alone on the CU: K / 32 steps of 512 MFMA cycles, in units of 2048 cycles (percent knob for experiments)
-    const int pct = su_env >= 0 ? su_env : 100;
-    const int st_units = (int)((a->K / 32) * 600 * pct / 100 / 2048);
-    dim3 grid((unsigned)gsz), block(256);
-    {
-        static int dbg = -1;
-        if (dbg < 0) dbg = mr_env_int("MR_G5_DEBUG", 0);
-        if (dbg == 1) {
-            dbg = 2;
-            int nb = -1;
-            hipError_t e_ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, g5::gemm5_kernel<5, 4>, 256, 0);
-            hipFuncAttributes fa_;
-            hipError_t e2_ = hipFuncGetAttributes(&fa_, reinterpret_cast<const void*>(g5::gemm5_kernel<5, 4>));
-            fprintf(stderr, "[gemm5] occupancy query: %d blocks / CU (err %d); regs %d, static LDS %zu, scratch %zu (err %d); grid %ld, stagger mode %d units %d\n", nb, (int)e_,
-                    fa_.numRegs, fa_.sharedSizeBytes, fa_.localSizeBytes, (int)e2_, (long)gsz, st_mode, st_units);
-        }
-    }
+void mr_gemm5_launch(const g256::G256Args& ga, bool r128, int mode, int st_mode, int st_units, int64_t grid_size, hipStream_t s) {
+    dim3 grid((unsigned)grid_size), block(256);
 #define G5_LAUNCH(MODE)                                                                                       \
     do {                                                                                                      \
         if (r128) hipLaunchKernelGGL((g5::gemm5_kernel<MODE, 4, 128, 8>), grid, block, 0, s, ga, st_mode, st_units); \
@@ -422,27 +297,4 @@ int mr_gemm5_launch(const mr_gemm_args* a, hipStream_t s) {
         default: G5_LAUNCH(5); break;
     }
 #undef G5_LAUNCH
-    mr_note_route(r128 ? "g5::gemm5_kernel<%d,4,128,8>" : "g5::gemm5_kernel<%d,4>", mode);
-    MR_CHECK_LAUNCH("mr_gemm (gemm5)");
-    return MR_OK;
-}
-
-// Which problems go to this kernel: mr_set_option("gemm5") 1 = every one it can take (tests, A/B), 0 = none, -1 = the policy below.
-bool mr_gemm5_wanted(const mr_gemm_args* a) {
-    static int env = -2;
-    if (env == -2) env = mr_env_int("MR_GEMM5", -1);
-    const int v = g_mr_opt_gemm5 >= 0 ? g_mr_opt_gemm5 : env;
-    if (v == 0 || a->colsum != nullptr && !a->aux) return false;
-    if (!mr_gemm5_takes(a)) return false;
-    if (v == 1 || v == 3) return true;
-    // Default policy (measured, scripts/micro/gemm3_test g5time): the few-tile short-K problems -- at most one 256 x 128 tile per CU, K <= 1024:
-    // the audio / span towers' 768-wide projections, the span and VCR-ViT QKV -- run 8-13 % faster here than on the one-barrier kernel's
-    // 96-wide tiles (16.3 vs 18.0, 20.6 vs 23.4, 15.3 vs 17.4, 24.5 vs 26.9 us); everything with more tiles or a longer K is slower
-    // (the 256 x 128 tile pair of a CU writes 1.5 x the operand bytes into LDS: DESIGN.md section 3).
-    // Round 4, 128 x 128 tiles: problems with at most one such tile per CU (M = 2308 / 3072, N = 768 / 1024, any K) run 25-40 % faster there than
-    // on either of the above (the header's table); with more tiles the 256-row geometries win (audio tower, M = 5952: 36-38 vs 52 us at K = 3072).
-    if (a->colsum != nullptr || a->M < 1024 || a->N < 256) return false;
-    if (g5_rows128(a)) return true;
-    const int64_t tiles = ((a->M + 255) / 256) * ((a->N + 127) / 128);
-    return tiles <= 256 && a->K <= 1024;
 }

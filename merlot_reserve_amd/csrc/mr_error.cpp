@@ -22,11 +22,12 @@ extern "C" const char* mr_last_error(void) { return g_err; }
 // 2: mr_gemm_args grew colsum / ldcs, mr_attention_bwd / mr_unit_norm_scale_bwd / mr_contrastive_lse gained arguments (round 2);
 // 3: mr_transpose_leaves, mr_set_option("gemm3") (round 3)
 // 4: handles (mr_create / mr_destroy / mr_make_current / mr_handle_set_option / mr_handle_get_option), mr_get_option,
-//    mr_last_gemm_kernel, options "gemm5" / "gemm5_stagger" / "gemm_trace"; environment knobs only in MR_DEBUG_ENV builds (round 4)
+//    mr_last_gemm_kernel, options "gemm5" / "gemm5_stagger" / "gemm_trace" (round 4)
 // 5: mr_attention_fwd_dense_mask, mr_masked_lm_xent, mr_crc32c / mr_crc32c_masked / mr_tfrecord_scan, option "attn_tile_modes"; mr_destroy refuses a handle
 //    another thread holds (round 5)
 // 6: mr_attention_bwd_dense_mask (+ _workspace), options "ln_impl" / "gemm_xpx" / "gemm_xpanel"; the dynamic symbol table is the header's names only (round 6)
-extern "C" int mr_version(void) { return 6; }
+// 7: the A/B-only options "gemm_v1_only" / "gemm5_stagger" / "gemm_xpx" / "gemm_xpanel" removed (mr_set_option on them: MR_EINVAL)
+extern "C" int mr_version(void) { return 7; }
 
 // ---- option sets: one per handle + the process-wide defaults ----
 static MrOptions g_default_opts;
@@ -38,19 +39,15 @@ mr_handle_s* mr_current_handle() { return g_current; }
 static int* opt_field(MrOptions& o, const char* name) {
     if (!name) return nullptr;
     if (!strcmp(name, "gemm_tile_n")) return &o.tile_n;
-    if (!strcmp(name, "gemm_v1_only")) return &o.v1_only;
     if (!strcmp(name, "gemm_group_tile_n")) return &o.group_tile_n;
     if (!strcmp(name, "gemm3")) return &o.gemm3;
     if (!strcmp(name, "gemm3_phases")) return &o.gemm3_ph;
     if (!strcmp(name, "gemm4")) return &o.gemm4;
     if (!strcmp(name, "gemm_cus")) return &o.gemm_cus;
     if (!strcmp(name, "gemm5")) return &o.gemm5;
-    if (!strcmp(name, "gemm5_stagger")) return &o.gemm5_stagger;
     if (!strcmp(name, "attn_onepass")) return &o.attn_onepass;
     if (!strcmp(name, "attn_tile_modes")) return &o.attn_tile_modes;
     if (!strcmp(name, "ln_impl")) return &o.ln_impl;
-    if (!strcmp(name, "gemm_xpx")) return &o.xpx;
-    if (!strcmp(name, "gemm_xpanel")) return &o.xpanel;
     if (!strcmp(name, "gemm_trace")) return &o.trace;
     return nullptr;
 }
@@ -153,12 +150,3 @@ void mr_note_route(const char* fmt, ...) {
 }
 extern "C" const char* mr_last_gemm_kernel(void) { return g_route; }
 
-int mr_env_int(const char* name, int dflt) {
-#ifdef MR_DEBUG_ENV
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}

@@ -150,7 +150,6 @@ static void time_g5(const Case& c, bool colsum, double budget_ms, double out_us[
         static bool init = false;
         if (!init) { init = true; if (const char* e = getenv("G5_COLS")) sscanf(e, "%d,%d,%d", &cols[1], &cols[2], &cols[3]); }
         mr_set_option("gemm5", cols[v]);
-        mr_set_option("gemm5_stagger", -1);
         { const char* e = getenv("G5_CUS"); mr_set_option("gemm_cus", (v && e) ? atoi(e) : 0); }      // G5_CUS=128: 256 workgroups = one per CU
         setup_args(&g, c, set, colsum);
         if (mr_gemm(&g, nullptr) != 0) { printf("mr_gemm failed: %s\n", mr_last_error()); exit(3); }
@@ -171,7 +170,6 @@ static void time_g5(const Case& c, bool colsum, double budget_ms, double out_us[
     }
     for (int v = 0; v < 4; ++v) out_us[v] = tot[v] * 1000.0 / n[v];
     mr_set_option("gemm5", -1);
-    mr_set_option("gemm5_stagger", -1);
     mr_set_option("gemm_cus", 0);
 }
 
@@ -289,13 +287,8 @@ int main(int argc, char** argv) {
             {1024, 256, 128, 3, "small"}, {1312, 3072, 128, 0, "four steps"}, {40000, 192, 128, 5, "four steps, narrow"}, {300, 192, 256, 1, "tiny ragged rot"},
         };
         mr_set_option("gemm5", getenv("G5_R128") ? atoi(getenv("G5_R128")) : 1);      // G5_R128=3: the 128 x 128 geometry
-        for (int st = 0; st < (getenv("G5_R128") ? 1 : 3); ++st) {
-            mr_set_option("gemm5_stagger", st);
-            char label[32]; snprintf(label, sizeof label, "g5/st%d", st);
-            for (const Case& c : checks) fails += check_case(c, label);
-        }
+        for (const Case& c : checks) fails += check_case(c, "g5");
         mr_set_option("gemm5", -1);
-        mr_set_option("gemm5_stagger", -1);
     }
     if (!strcmp(what, "g5time") || !strcmp(what, "g5")) {
         const Case shapes[] = {
@@ -325,38 +318,6 @@ int main(int argc, char** argv) {
         }
     }
 
-    if (!strcmp(what, "g5stamps")) {
-        // in-kernel timeline of the two workgroups of a CU (library built with -DMR_G5_STAMPS): per tile, k-loop start / end, epilogue end
-        const int mode = argc > 2 ? atoi(argv[2]) : 2, st = argc > 3 ? atoi(argv[3]) : 1;
-        const Case c = {15424, 3072, 768, mode, "stamps"};
-        mr_gemm_args g;
-        mr_set_option("gemm5", 1);
-        mr_set_option("gemm5_stagger", st);
-        for (int r = 0; r < 20; ++r) { setup_args(&g, c, r % 3, mode == 4); mr_gemm(&g, nullptr); }
-        CK(hipDeviceSynchronize());
-        CK(hipMemset(dWs, 0, 512 * 8 * 4 * 8));
-        setup_args(&g, c, 0, mode == 4);
-        mr_gemm(&g, nullptr);
-        CK(hipDeviceSynchronize());
-        std::vector<unsigned long long> h(512 * 8 * 4);
-        CK(hipMemcpy(h.data(), dWs, h.size() * 8, hipMemcpyDeviceToHost));
-        unsigned long long t0 = ~0ull;
-        for (int b = 0; b < 512; ++b) if (h[b * 32] && h[b * 32] < t0) t0 = h[b * 32];
-        printf("mode %d stagger %d: blocks b and b + 256 share a CU; cycles from the first k-loop start\n", mode, st);
-        for (int b : {0, 1, 8, 100, 255}) {
-            for (int w = 0; w < 2; ++w) {
-                const int bb = b + 256 * w;
-                printf("  block %3d:", bb);
-                for (int q = 0; q < 4; ++q) {
-                    const unsigned long long* e = &h[(bb * 8 + q) * 4];
-                    if (!e[0]) break;
-                    printf("  [k %6llu-%6llu e -%6llu]", e[0] - t0, e[1] - t0, e[2] - t0);
-                }
-                printf("\n");
-            }
-        }
-        mr_set_option("gemm5", -1); mr_set_option("gemm5_stagger", -1);
-    }
     if (!strcmp(what, "tn") || !strcmp(what, "all")) {
         // weight gradients of a layer (x 2 layers): A = activations [K = tokens, in], B = upstream gradients [K, out]
         struct WG { int64_t M, N; };
@@ -468,45 +429,6 @@ int main(int argc, char** argv) {
             time_variants(c, false, reps * 10.0, t);
             printf("kloop %-16s g4/256 %7.1f us   g4/192 %7.1f us   | g3/256 %7.1f us  g3/192 %7.1f us\n", c.name, t[1], t[2], t[0], t[3]);
         }
-    }
-    if (!strcmp(what, "stamps")) {       // needs the MR_G3_STAMPS build of the library
-        const Case shapes[] = {{15424, 3072, 768, 5, "fc1 plain"}, {15424, 3072, 768, 2, "fc1 fwd gelu+c2"}, {15424, 768, 3072, 3, "fc2 fwd residual"}, {8192, 8192, 8192, 5, "8192^3"}};
-        const int widths[] = {256, 192};
-        for (const Case& c : shapes) for (int w : widths) {
-            mr_set_option("gemm3", w);
-            mr_gemm_args g;
-            for (int r = 0; r < 3; ++r) { setup_args(&g, c, r, false); mr_gemm(&g, nullptr); }
-            CK(hipMemset(dWs, 0, 2 << 20));
-            setup_args(&g, c, 0, false);
-            mr_gemm(&g, nullptr);
-            CK(hipDeviceSynchronize());
-            std::vector<unsigned long long> st(256 * 2 * 8 * 4);
-            CK(hipMemcpy(st.data(), dWs, st.size() * 8, hipMemcpyDeviceToHost));
-            const int nkt = (int)(c.K / 64);
-            double kl[2] = {0, 0}, ep[2] = {0, 0}, gap[2] = {0, 0}, span = 0; int n[2] = {0, 0}, ng[2] = {0, 0}, nb = 0;
-            for (int b = 0; b < 256; ++b) for (int wr = 0; wr < 2; ++wr) {
-                const unsigned long long* q = &st[((b * 2 + wr) * 8) * 4];
-                int last = -1;
-                for (int i = 0; i < 8 && q[i * 4]; ++i) {
-                    kl[wr] += (double)(q[i * 4 + 1] - q[i * 4]); ep[wr] += (double)(q[i * 4 + 2] - q[i * 4 + 1]); ++n[wr];
-                    if (i > 0) { gap[wr] += (double)(q[i * 4] - q[(i - 1) * 4 + 2]); ++ng[wr]; }
-                    last = i;
-                }
-                if (wr == 0 && last >= 0) { span += (double)(q[last * 4 + 2] - q[0]); ++nb; }
-            }
-            if (w == 256) {
-                std::vector<unsigned long long> ks(8 * 4 * 16);
-                CK(hipMemcpy(ks.data(), (unsigned long long*)dWs + 65536, ks.size() * 8, hipMemcpyDeviceToHost));
-                for (int b = 0; b < 2; ++b) for (int i = 0; i < 3; ++i) {
-                    printf("   k-tile cycles, block %d tile %d:", b, i);
-                    for (int t = 1; t < 16 && t < nkt && ks[(b * 4 + i) * 16 + t]; ++t) printf(" %5llu", ks[(b * 4 + i) * 16 + t] - ks[(b * 4 + i) * 16 + t - 1]);
-                    printf("\n");
-                }
-            }
-            printf("stamps %-18s g3/%d: per tile  k-loop %8.0f / %8.0f cyc (%5.0f per k-tile)  epilogue %7.0f / %7.0f  gap %6.0f / %6.0f   (group 0 / 1; s_memtime ticks = 10 ns);  block span %8.0f\n",
-                   c.name, w, kl[0] / n[0], kl[1] / n[1], kl[0] / n[0] / nkt, ep[0] / n[0], ep[1] / n[1], ng[0] ? gap[0] / ng[0] : 0., ng[1] ? gap[1] / ng[1] : 0., span / nb);
-        }
-        mr_set_option("gemm3", 1);
     }
     printf(fails ? "FAILED (%d)\n" : "ALL OK\n", fails);
     return fails ? 1 : 0;

@@ -1,6 +1,6 @@
 """Minimal reproducer attempt for the packed-fp32 LayerNorm hazard of DESIGN.md section 4 (round 3: a few LayerNorm rows per launch off by 1-7 bf16 ulp,
 only while a second queue's kernels shared the chip, only in the SLP-vectorised build of layernorm.hip).
-    bash scripts/build_diag.sh slp layernorm                      # layernorm.hip WITHOUT -fno-slp-vectorize -> merlot_reserve_amd/libdiag_slp.so
+    # a library with layernorm.hip built WITHOUT -fno-slp-vectorize (EXTRA_FLAGS in merlot_reserve_amd/build.py) -> merlot_reserve_amd/libdiag_slp.so
     MR_LIB=merlot_reserve_amd/libdiag_slp.so python scripts/slp_repro.py     # packed build
     python scripts/slp_repro.py                                              # shipped (scalar) build
 ln_fwd / ln_bwd of the base step's shape on stream A, launched REPS times while stream B runs a loop of the step's big GEMMs (persistent whole-CU

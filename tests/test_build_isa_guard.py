@@ -65,9 +65,9 @@ def test_register_spills_are_listed_and_cold():
         assert any(re.search(rx, k) for rx in allowed_hot), f'scratch traffic in an MFMA block of {k}'
 
 
-def test_flag_stamp_triggers_rebuild(monkeypatch):
-    """Toggling MR_DEBUG_ENV changes the stamp build() compares: a debug library cannot be left in place as the product (or the reverse)."""
+def test_changed_extra_flags_trigger_rebuild(monkeypatch):
+    """A changed flag set changes the stamp build() compares: a library built with other flags cannot be left in place."""
     _fresh_build()
     assert not B._needs_build()
-    monkeypatch.setenv('MR_DEBUG_ENV', '1')
+    monkeypatch.setattr(B, 'EXTRA_FLAGS', {**B.EXTRA_FLAGS, 'gemm.hip': ['-fno-slp-vectorize']})
     assert B._needs_build()
