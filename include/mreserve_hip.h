@@ -261,6 +261,20 @@ int mr_split_f32_to_bf16_hilo(const float* src, void* hi, void* lo, int64_t n, v
 int mr_split_f32_to_bf16_hilo_rows(const float* src, int64_t lds, void* hi, void* lo, int64_t ldo, int64_t rows, int64_t cols,
                                    void* stream);
 
+/* ---- step metrics ring (the lagged log of pretrain/train.py:119-129 for a step that is one replayed hipGraph) ----
+ * ONE launch copies one step's RAW metric sources into one row of a device ring; which row is decided on the device, so a
+ * replayed graph needs no host write per step:
+ *   step = *counter;  row = step mod depth;  *counter = step + 1;  row_steps[row] = step;
+ *   ring[row, 0:3] = loss_acc[0:3];  ring[row, 3:15] = diag[0:12] (the [2, 6] sums / counts of mr_contrastive_lse);
+ *   ring[row, 15:18] = scales[0:3] (fp32 master contrastive_scales);  ring[row, 18] = sched[0];  columns >= 19 are left alone.
+ * All pointers are device pointers; ring is [depth, row_len] fp32 with row_len >= MR_METRICS_ROW; row_steps [depth] and counter [1]
+ * are int32.  The host sets *counter once (0, or the restored step) and derives the log record from the raw row.  One wave,
+ * plain loads and stores, no atomics: launches that share a counter must be ordered on one stream.
+ * MR_EINVAL (no launch) for a null pointer, depth <= 0 or row_len < MR_METRICS_ROW. */
+#define MR_METRICS_ROW 19
+int mr_metrics_push(const float* loss_acc, const float* diag, const float* scales, const float* sched, float* ring,
+                    int32_t* row_steps, int32_t* counter, int64_t depth, int64_t row_len, void* stream);
+
 /* ---- optimizer: nan_to_num + bf16-state Adam + weight decay + schedule + apply (P:328, O:54-114, 180-195) ----
  * Flat buffers of n elements (n % 2048 == 0): master fp32 params, bf16 grads, bf16 mu, bf16 cube-coded nu.
  * decay_flag_per_block: one uint8 per 2048-element block (1 = weight decay applies: leaf ndim > 1, O:182-184).

@@ -149,9 +149,11 @@ def latest_checkpoint(ckpt_dir, prefix='ckpt_'):
     return os.path.join(ckpt_dir, sorted(names, key=_natural_key)[-1]) if names else None
 
 
-def save_checkpoint(state, path, keep=None, overwrite=True, no_optimizer=False, prefix='ckpt_', rank=None):
+def save_checkpoint(state, path, keep=None, overwrite=True, no_optimizer=False, prefix='ckpt_', rank=None, keep_fp32=False):
     """state: {'step': int, 'params': tree, 'opt_state': tree or None} (or an object with those attributes / a
     .state_dict()).  fp32 leaves are written as fp16 (checkpoint.py:26-37), bf16 leaves unchanged.
+    keep_fp32 = True writes fp32 leaves as fp32 instead -- same layout, read by load_checkpoint as it is: the restart file of
+    merlot_reserve_amd.train, from which a run resumes bit for bit (the fp16 form rounds the master parameters and overflows above 65504).
 
     Data-parallel runs: with partitioned Adam moments (Trainer(shard_optimizer=True), MerlotReserveVCR(shard_optimizer=True))
     `state.state_dict()` gathers the moments from every rank -- a COLLECTIVE -- so EVERY rank must call save_checkpoint; pass `rank=`
@@ -163,7 +165,9 @@ def save_checkpoint(state, path, keep=None, overwrite=True, no_optimizer=False, 
     if rank is not None and int(rank) != 0:
         return os.path.join(path, f'{prefix}{step}')
     sd = {'step': step, 'params': state['params'], 'opt_state': None if no_optimizer else state.get('opt_state')}
-    sd = _treemap_cast(torch.float32, torch.float16, tree_map(lambda x: _as_tensor(x) if isinstance(x, (torch.Tensor, np.ndarray)) else x, sd))
+    sd = tree_map(lambda x: _as_tensor(x) if isinstance(x, (torch.Tensor, np.ndarray)) else x, sd)
+    if not keep_fp32:
+        sd = _treemap_cast(torch.float32, torch.float16, sd)
     os.makedirs(path, exist_ok=True)
     fn = os.path.join(path, f'{prefix}{step}')
     if os.path.exists(fn) and not overwrite:

@@ -726,3 +726,41 @@ extern "C" int mr_contrastive_lse(float* logits, int64_t ldl, int64_t L, int64_t
     MR_CHECK_LAUNCH("mr_contrastive_lse");
     return MR_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- step metrics ring
+// One step's RAW metric sources -> one row of a device ring (the host derives the log record, trainer.Trainer.drain_metrics).  The row
+// index comes from a counter in device memory that this kernel advances, so a replayed hipGraph needs no host write per step.
+// One wave: every lane reads the counter, the barrier orders those reads before lane 0 stores the new value.
+namespace {
+__global__ __launch_bounds__(64) void metrics_push_kernel(const float* __restrict__ loss_acc, const float* __restrict__ diag,
+                                                          const float* __restrict__ scales, const float* __restrict__ sched,
+                                                          float* __restrict__ ring, int32_t* __restrict__ row_steps,
+                                                          int32_t* counter, int depth, int row_len) {
+    const int lane = threadIdx.x;
+    const int32_t step = *counter;
+    __syncthreads();
+    int row = step % depth;
+    if (row < 0) row += depth;
+    float* dst = ring + (int64_t)row * row_len;
+    if (lane < 3) dst[lane] = loss_acc[lane];
+    else if (lane < 15) dst[lane] = diag[lane - 3];
+    else if (lane < 18) dst[lane] = scales[lane - 15];
+    else if (lane == 18) dst[lane] = sched[0];
+    if (lane == 0) {
+        row_steps[row] = step;
+        *counter = step + 1;
+    }
+}
+}  // namespace
+
+extern "C" int mr_metrics_push(const float* loss_acc, const float* diag, const float* scales, const float* sched, float* ring,
+                               int32_t* row_steps, int32_t* counter, int64_t depth, int64_t row_len, void* stream) {
+    MR_CHECK_ARG(loss_acc && diag && scales && sched && ring && row_steps && counter, "mr_metrics_push: null pointer");
+    MR_CHECK_ARG(depth > 0 && depth <= (1 << 20), "mr_metrics_push: depth must be in [1, 2^20], got %lld", (long long)depth);
+    MR_CHECK_ARG(row_len >= MR_METRICS_ROW && row_len <= (1 << 10), "mr_metrics_push: row_len must be in [%d, 1024], got %lld",
+                 MR_METRICS_ROW, (long long)row_len);
+    hipLaunchKernelGGL(metrics_push_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), loss_acc, diag, scales, sched,
+                       ring, row_steps, counter, (int)depth, (int)row_len);
+    MR_CHECK_LAUNCH("mr_metrics_push");
+    return MR_OK;
+}

@@ -791,8 +791,10 @@ class PretrainEngine(TowerEngine):
 
     def loss_info(self):
         """Host dict like the reference's loss_info (pretrain_model.py:263-303) from the device accumulators."""
-        la = self.loss_acc.tolist()
-        dg = self.diag.tolist()
+        return self.info_from(self.loss_acc.tolist(), self.diag.tolist())
+
+    def info_from(self, la, dg):
+        """The dict of loss_info() from host copies of loss_acc [3] and diag [2][6] (also the rows of the trainer's metrics ring)."""
         info = {k: la[i] for i, (k, *_r) in enumerate(self.objectives)}
         for i, t in enumerate(['text2audio', 'audio2text', 'random_text']):
             info[f'_stuff_to_span_from_{t}'] = sum(dg[di][i] / (dg[di][3 + i] + 1e-5) / 2.0 for di in range(2))

@@ -645,3 +645,17 @@ def adam_bf16_update_dev(master, work, grad, mu, nu, orig, decay_flags, b1, b2, 
     check(_lib.load().mr_adam_bf16_update_dev(master.data_ptr(), work.data_ptr(), grad.data_ptr(), mu.data_ptr(), nu.data_ptr(),
                                               _ptr(orig), decay_flags.data_ptr(), master.numel(), b1, b2, eps, weight_decay,
                                               hyper.data_ptr(), _stream()), 'mr_adam_bf16_update_dev')
+
+
+METRICS_ROW = 19        # MR_METRICS_ROW: loss_acc[3] | diag[2, 6] | contrastive_scales[3] | schedule scalar
+
+
+@_timed('rowops')
+def metrics_push(loss_acc, diag, scales, sched, ring, row_steps, counter):
+    """One step's raw metric sources -> row (counter mod depth) of ring [depth, row_len] fp32; row_steps[row] = counter; counter += 1
+    (all on the device: include/mreserve_hip.h, mr_metrics_push)."""
+    assert all(t.dtype == F32 and t.is_contiguous() for t in (loss_acc, diag, scales, sched, ring))
+    assert loss_acc.numel() >= 3 and diag.numel() >= 12 and scales.numel() >= 3 and sched.numel() >= 1
+    assert row_steps.dtype == torch.int32 and counter.dtype == torch.int32 and ring.dim() == 2 and row_steps.numel() >= ring.shape[0]
+    check(_lib.load().mr_metrics_push(loss_acc.data_ptr(), diag.data_ptr(), scales.data_ptr(), sched.data_ptr(), ring.data_ptr(),
+                                      row_steps.data_ptr(), counter.data_ptr(), ring.shape[0], ring.shape[1], _stream()), 'mr_metrics_push')
