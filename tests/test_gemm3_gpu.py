@@ -48,12 +48,22 @@ def forced(request):
     lib.mr_set_option(b'gemm_trace', 0)
 
 
-def routed_as_forced(forced, K):
-    """The launch went to the kernel the fixture asked for (gemm5 takes K % 64 == 0, K >= 128; shorter K falls to the ping-pong kernel)."""
+def routed_as_forced(forced, K, mode=5):
+    """The launch went to the kernel INSTANCE the fixture asked for.  mode: the epilogue of the launch as csrc/gemm_route.cpp numbers it (0 bias,
+    1 bias + "rotary", 2 bias + GELU + c2, 3 residual, 4 aux, 5 plain product).  gemm5 takes K % 64 == 0, K >= 128 (a shorter K falls to the ping-pong
+    kernel); gemm4 has the plain, residual and 192-wide bias epilogues (anything else stays on the ping-pong kernel, at the schedule the router chooses);
+    the ping-pong kernel runs a plain product as mode 0 and has no one-phase 256-wide aux instance."""
     from merlot_reserve_amd import _lib
     name = _lib.load().mr_last_gemm_kernel().decode()
-    if forced[3] and K % 64 == 0 and K >= 128:
-        assert name.startswith('g5::gemm5_kernel') and name.endswith(',128,8>') == (forced[3] == 3), name
+    width, phases, g4, g5 = forced
+    if g5 and K % 64 == 0 and K >= 128:
+        assert name == (f'g5::gemm5_kernel<{mode},4,128,8>' if g5 == 3 else f'g5::gemm5_kernel<{mode},4>'), name
+    elif g4 and mode in (0, 3, 5) and not (width == 256 and mode == 0):
+        assert name == f'g4::gemm4_kernel<{width},{mode}>', name
+    else:
+        m3 = 0 if mode == 5 else mode
+        ph = 2 if (m3 == 4 and width == 256) else (phases or (2 if K >= 8192 else 1))
+        assert name == f'g3::gemm3_kernel<{width},{m3},{ph}>', name
 
 
 @pytest.fixture
@@ -93,9 +103,11 @@ def test_nt_epilogues(dev, forced):
     ref = a.float() @ w.float().T
     out = torch.zeros(M, N, dtype=BF16, device=dev)
     ops.gemm(a, w, out, transB=True, bias=bias)
+    routed_as_forced(forced, K, 0)
     assert_close(out, ref + bias.float(), 3e-3, 'bias')
     tab = torch.rand(S, 32, device=dev) * 2 - 1                    # the "rotary" diagonal scaling of q and k (M:118-136)
     ops.gemm(a, w, out, transB=True, bias=bias, rot_tab=tab, rot_cols=512)
+    routed_as_forced(forced, K, 1)
     scale = torch.ones(M, N, device=dev)
     rows = torch.arange(M, device=dev) % S
     for h in range(512 // 64):
@@ -103,7 +115,7 @@ def test_nt_epilogues(dev, forced):
     assert_close(out, (ref + bias.float()) * scale, 3e-3, 'bias + rot')
     pre = torch.zeros(M, N, dtype=BF16, device=dev)
     ops.gemm(a, w, out, transB=True, bias=bias, act=ops.ACT_GELU, c2=pre)
-    routed_as_forced(forced, K)
+    routed_as_forced(forced, K, 2)
     x = ref + bias.float()
     sg = torch.sigmoid(1.702 * x)
     assert_close(out, x * sg, 4e-3, 'gelu')
@@ -111,12 +123,13 @@ def test_nt_epilogues(dev, forced):
     res = rnd((M, N), dev, seed=9)
     buf = res.clone()
     ops.gemm(a, w, buf, transB=True, residual=buf)
+    routed_as_forced(forced, K, 3)
     assert_close(buf, ref.to(BF16).float() + res.float(), 3e-3, 'residual in place')
     aux = rnd((M, N), dev, seed=10)
     nrows = _lib.load().mr_gemm_colsum_rows(M)
     cs = torch.full((nrows, N), float('nan'), device=dev)
     ops.gemm(a, w, out, transB=True, aux=aux, colsum=cs)
-    routed_as_forced(forced, K)
+    routed_as_forced(forced, K, 4)
     assert_close(out, ref.to(BF16).float() * aux.float(), 4e-3, 'aux multiply')
     assert_close(cs.sum(0), out.float().sum(0), 2e-3, 'column sums of the stored output')
     ops.gemm(a, w, out, transB=True, aux=aux)
