@@ -21,6 +21,10 @@ Program: ViT (S = h*w + 1) + attention pool -> [B, V, H]; ONE index-driven gathe
 [T text tokens | V vision tokens] (the 8-fold `repeat` of the image rows, F:157, is just the gather list);
 joint encoder with one validity code per position; the row at the first MASK of every sequence; Dense(1); softmax
 cross-entropy over the A answers; hand-written backward through the same kernels as the pretraining step.
+
+The step itself (finetune_train_step, the scanned step, FinetuneTrainState, FinetuneGraphStep) is shared with the TVQA model of
+tvqa.py: it asks the model's engine (a FinetuneEngine) for its backward stages and their gradient buckets, its metric names, how to
+slice one example out of a batch and which batch entries live on the device.
 """
 import numpy as np
 import torch
@@ -54,6 +58,7 @@ class VCRDims:
         self.A = d.get('num_answers', 4)
         self.T = d['lang_seq_len']
         self.n = B * 2 * self.A
+        self.Nv = B                                   # images
         self.Sv, self.Sj = self.hw + 1, self.T + self.V
         self.Lv, self.Lj = m['vit_num_layers'], m['joint_num_layers']
 
@@ -83,7 +88,69 @@ def build_vcr_plan(answers, d):
     return plan
 
 
-class VCREngine(TowerEngine):
+class FinetuneEngine(TowerEngine):
+    """What the finetuning programs (VCR here, TVQA in tvqa.py) share, and what the shared step (finetune_train_step, FinetuneGraphStep)
+    asks of an engine.  A subclass sets: metric_names (the keys of loss_info()), device_keys (the batch entries that live on the device, in
+    the order forward_device takes them), batch_size / slice_example (the size of a batch and one example of it), build_plan,
+    forward_device, loss_and_grad_logits, backward_stages (the third field of a stage marks the vision tower's: the only one whose layers
+    are cut into ('vision', l) buckets), gradient_buckets; and the buffers named below."""
+
+    def _idx_capacity(self):
+        return self.tj.M + 64
+
+    def upload(self, batch, plan=None):
+        """The host part of a step: the plan's index lists and the labels into their persistent device buffers."""
+        self.set_plan(plan if plan is not None else self.build_plan(batch))
+        self.labels_dev.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(batch['labels']).astype(np.int32).reshape(-1))), non_blocking=True)
+
+    def forward(self, batch, plan=None):
+        self.upload(batch, plan)
+        return self.forward_device(*[batch[k] for k in self.device_keys])
+
+    def backward(self):
+        for stage, _key, _cuts in self.backward_stages():
+            stage()
+
+    def _buckets_with_vision_cuts(self, head):
+        """`head` (the buckets in front of the vision tower) + the vision tower cut at 2/3 and 1/3 of its depth + 'vision_end' = the rest."""
+        p, Lv = self.p, self.d.Lv
+        v0, v1 = p.tower_ranges['vision_encoder']
+        assert v1 == p.total and head[-1][2] == v0
+        cuts = sorted({l for l in (Lv - Lv // 3, Lv - 2 * (Lv // 3)) if 0 < l < Lv}, reverse=True)
+        lo_of = lambda l: p.offsets[f'vision_encoder/transformer/layer_{l:02d}/pre_attn_ln/scale'][0]
+        buckets, hi = list(head), v1
+        for l in cuts:
+            buckets.append((('vision', l), lo_of(l), hi))
+            hi = lo_of(l)
+        buckets.append(('vision_end', v0, hi))
+        assert sum(b[2] - b[1] for b in buckets) == p.total and all(b[1] % 2048 == 0 and b[2] % 2048 == 0 for b in buckets)
+        return buckets, cuts
+
+    def backward_stage_vision(self, layer_done=None):
+        d, G, tv = self.d, self.p.g, self.tv
+        tr = self._begin_tower_reductions()
+        Dv = self._tower_with_pool_backward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.vit_rot, self.vit_pool_rows,
+                                            self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po, self.v_probs, self.d_imgs_seq,
+                                            self.d_v_cls, self.Dv, layer_done=layer_done, tr=tr)
+        Dp = self.cur.Dpatch[:d.Nv * d.hw]
+        ops.segment_sum([Dv], self.unpad_v[0], self.unpad_v[1], Dp)
+        self._t_colsum(tr, Dp, G['vision_encoder/embedding/bias'])
+        self._flush_tower_reductions(tr)
+        self.gemm(self._images2d, Dp, G['vision_encoder/embedding/kernel'], transA=True)
+
+
+class VCREngine(FinetuneEngine):
+    metric_names = ('loss', 'is_right')
+    device_keys = ('image',)
+
+    @staticmethod
+    def batch_size(batch):
+        return int(batch['image'].shape[0])
+
+    @staticmethod
+    def slice_example(batch, i):
+        return {'image': batch['image'][i:i + 1], 'answers': np.asarray(batch['answers'])[i:i + 1], 'labels': np.asarray(batch['labels'])[i:i + 1]}
+
     def __init__(self, config, B, params, device):
         self.config, self.p, self.dev = config, params, torch.device(device)
         self.d = d = VCRDims(config, B)
@@ -127,16 +194,8 @@ class VCREngine(TowerEngine):
         self.side_stream = None
         self.plan_dev, self._plan_caps, self._plan_views, self.plan_frozen = None, {}, {}, False
 
-    def _idx_capacity(self):
-        return self.tj.M + 64
-
-    def forward(self, batch, plan=None):
-        d, W = self.d, self.W
-        if plan is None:
-            plan = build_vcr_plan(batch['answers'], d)
-        self.set_plan(plan)
-        self.labels_dev.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(batch['labels']).astype(np.int32).reshape(-1))), non_blocking=True)
-        return self.forward_device(batch['image'])
+    def build_plan(self, batch):
+        return build_vcr_plan(batch['answers'], self.d)
 
     def forward_device(self, image):
         d, W, tv, tj = self.d, self.W, self.tv, self.tj
@@ -157,25 +216,15 @@ class VCREngine(TowerEngine):
         ops.softmax_xent(self.logits, d.A * 8, 8, self.labels_dev, 2 * d.B, d.A, 1.0 / (2 * d.B), self.loss_acc[0:1], self.loss_acc[1:2], self.dlogits)
         return self.loss_acc
 
-    def backward(self):
-        self.backward_stage_joint()
-        self.backward_stage_vision()
+    def backward_stages(self):
+        """[(stage, the bucket of gradient_buckets() that is final after it, whether it is the VISION tower's stage: that one takes
+        layer_done and the step hands over the ('vision', l) buckets of _buckets_with_vision_cuts from it)]"""
+        return [(self.backward_stage_joint, 'joint', False), (self.backward_stage_vision, 'vision_end', True)]
 
     def gradient_buckets(self):
         """Ranges of the flat gradient buffer in the order backward makes them final (like trainer.Trainer._make_buckets):
         'joint' = [proj, joint tower, token table]; the vision tower cut at 2/3 and 1/3 of its depth; 'vision_end' = the rest."""
-        p, Lv = self.p, self.d.Lv
-        v0, v1 = p.tower_ranges['vision_encoder']
-        assert v1 == p.total
-        cuts = sorted({l for l in (Lv - Lv // 3, Lv - 2 * (Lv // 3)) if 0 < l < Lv}, reverse=True)
-        lo_of = lambda l: p.offsets[f'vision_encoder/transformer/layer_{l:02d}/pre_attn_ln/scale'][0]
-        buckets, hi = [('joint', 0, v0)], v1
-        for l in cuts:
-            buckets.append((('vision', l), lo_of(l), hi))
-            hi = lo_of(l)
-        buckets.append(('vision_end', v0, hi))
-        assert sum(b[2] - b[1] for b in buckets) == p.total and all(b[1] % 2048 == 0 and b[2] % 2048 == 0 for b in buckets)
-        return buckets, cuts
+        return self._buckets_with_vision_cuts([('joint', 0, self.p.tower_ranges['vision_encoder'][0])])
 
     def backward_stage_joint(self):
         d, W, G, tj = self.d, self.W, self.p.g, self.tj
@@ -191,26 +240,25 @@ class VCREngine(TowerEngine):
         ops.segment_sum([Dj], self._pl('embT_indptr'), self._pl('embT_idx'), G['token_encoder/Embed_0/embedding'])
         ops.segment_sum([Dj], self.visT[0], self.visT[1], self.d_imgs_seq)
 
-    def backward_stage_vision(self, layer_done=None):
-        d, G, tv = self.d, self.p.g, self.tv
-        tr = self._begin_tower_reductions()
-        Dv = self._tower_with_pool_backward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.vit_rot, self.vit_pool_rows,
-                                            self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po, self.v_probs, self.d_imgs_seq,
-                                            self.d_v_cls, self.Dv, layer_done=layer_done, tr=tr)
-        Dp = self.cur.Dpatch[:d.B * d.hw]
-        ops.segment_sum([Dv], self.unpad_v[0], self.unpad_v[1], Dp)
-        self._t_colsum(tr, Dp, G['vision_encoder/embedding/bias'])
-        self._flush_tower_reductions(tr)
-        self.gemm(self._images2d, Dp, G['vision_encoder/embedding/kernel'], transA=True)
-
     def loss_info(self):
         la = self.loss_acc.tolist()
         return {'loss': la[0], 'is_right': la[1]}
 
 
+def _mean_over_ranks(info, eng, comm):
+    """The step's metrics averaged over the ranks of `comm` (FO:187-189)."""
+    if comm is None or comm.world <= 1:
+        return info
+    t = torch.tensor([info[k] for k in eng.metric_names], dtype=torch.float32, device=eng.dev)
+    comm.allreduce_mean(t)
+    return {k: float(v) for k, v in zip(eng.metric_names, t)}
+
+
 # ------------------------------------------------------------------------------------------------ reference-named API
 class MerlotReserveVCR:
     """F:144-170"""
+    engine_cls = VCREngine
+    param_specs = staticmethod(vcr_param_specs)
 
     def __init__(self, config, device='cuda:0', rank=0, world=1, comm=None, seed=0, shard_optimizer=False):
         """shard_optimizer = True: the Adam moments are partitioned over the ranks of `comm` (FO:148-171; zero.py)."""
@@ -226,11 +274,11 @@ class MerlotReserveVCR:
         return cls(config, **kwargs)
 
     def _ensure(self, batch):
-        B = int(batch['image'].shape[0])
+        B = self.engine_cls.batch_size(batch)
         if self.engine is None:
-            self.params_store = ParamStore(self.config, self.device, seed=self.seed, specs=vcr_param_specs(self.config),
+            self.params_store = ParamStore(self.config, self.device, seed=self.seed, specs=self.param_specs(self.config),
                                            decay_rule=decay_finetune, with_orig=True, with_optimizer=not self.shard_optimizer)
-            self.engine = VCREngine(self.config, B, self.params_store, self.device)
+            self.engine = self.engine_cls(self.config, B, self.params_store, self.device)
             if self.shard_optimizer:
                 from .zero import MomentShards
                 self.shards = MomentShards(self.params_store, self.engine.gradient_buckets()[0], self.comm)
@@ -389,8 +437,9 @@ def train_loss_fn(state, params, batch):
 def _backward_reduce_update(state):
     """Backward from the engine's dlogits with every finished gradient BUCKET handed to a second stream: nan_to_num ->
     all-reduce(mean) over ranks (FO:148-149) -> the optimizer chain on that range (FO:77-90), while the main stream goes on with
-    the vision tower's backward.  Four buckets in ONE program order on ONE stream, the same on every rank; with the library's RCCL
-    communicator the whole sequence is capturable (VCRGraphStep)."""
+    the next stage of backward (engine.backward_stages(): VCR joint -> vision, four buckets; TVQA joint -> audio -> vision, five).
+    The buckets in ONE program order on ONE stream, the same on every rank; with the library's RCCL communicator the whole sequence
+    is capturable (FinetuneGraphStep)."""
     model = state._model
     eng, comm, p = model.engine, model.comm, model.params_store
     main = torch.cuda.current_stream()
@@ -412,11 +461,16 @@ def _backward_reduce_update(state):
                 model.shards.update(key, state.apply_shard)
             else:
                 state.apply_range(lo, hi)
-    eng.backward_stage_joint()
-    finish('joint')
-    with ops.gemm_cus(comm.world if comm is not None else 1):      # a bucket's all-reduce runs beside the vision tower's GEMMs
-        eng.backward_stage_vision(layer_done=lambda l: finish(('vision', l)) if l in cuts else None)
-        finish('vision_end')
+    stages = eng.backward_stages()
+    stages[0][0]()
+    finish(stages[0][1])
+    with ops.gemm_cus(comm.world if comm is not None else 1):      # a bucket's all-reduce runs beside the next towers' GEMMs
+        for stage, key, is_vision in stages[1:]:
+            if is_vision:
+                stage(layer_done=lambda l: finish(('vision', l)) if l in cuts else None)
+            else:
+                stage()
+            finish(key)
     main.wait_stream(cs)
 
 
@@ -433,20 +487,14 @@ def finetune_train_step(state, batch, loss_fn=None, tx_fns=None, scan_minibatch=
     state.prepare_step()
     _backward_reduce_update(state)
     state.step += 1
-    info = eng.loss_info()
-    comm = model.comm
-    if comm is not None and comm.world > 1:
-        t = torch.tensor([info['loss'], info['is_right']], dtype=torch.float32, device=eng.dev)
-        comm.allreduce_mean(t)
-        info = {'loss': float(t[0]), 'is_right': float(t[1])}
-    return state, info
+    return state, _mean_over_ranks(eng.loss_info(), eng, model.comm)
 
 
 def _finetune_train_step_scanned(state, batch):
     model = state._model
     eng, comm, p = model.engine, model.comm, model.params_store
     if getattr(model, '_engine1', None) is None:              # an engine for ONE example on the same parameter store
-        model._engine1 = VCREngine(model.config, 1, p, model.device)
+        model._engine1 = type(eng)(model.config, 1, p, model.device)
     e1 = model._engine1
     # Memory: the one-example engine keeps its own activations / scratch beside the B-example one (the price of scan_minibatch here:
     # ~1/B of the big engine's activations; free it with `model._engine1 = None` when scanning is switched off), and ONE persistent
@@ -457,7 +505,7 @@ def _finetune_train_step_scanned(state, batch):
     acc.zero_()
     losses = []
     for i in range(eng.d.B):
-        micro = {'image': batch['image'][i:i + 1], 'answers': np.asarray(batch['answers'])[i:i + 1], 'labels': np.asarray(batch['labels'])[i:i + 1]}
+        micro = eng.slice_example(batch, i)
         p.grad.zero_()                                        # a leaf this example's backward does not write must contribute 0, not the previous example's value
         e1.forward(micro)
         e1.loss_and_grad_logits()
@@ -476,19 +524,15 @@ def _finetune_train_step_scanned(state, batch):
         state.apply_range(0, p.total)
     state.step += 1
     info = {k: float(np.mean([l[k] for l in losses])) for k in losses[0]}
-    if comm is not None and comm.world > 1:
-        t = torch.tensor([info['loss'], info['is_right']], dtype=torch.float32, device=eng.dev)
-        comm.allreduce_mean(t)
-        info = {'loss': float(t[0]), 'is_right': float(t[1])}
-    return state, info
+    return state, _mean_over_ranks(info, eng, comm)
 
 
-class VCRGraphStep:
+class FinetuneGraphStep:
     """hipGraph replay of finetune_train_step: the step is a fixed launch sequence over fixed buffers, so forward + loss + backward +
-    the four bucket reductions + the optimizer are captured ONCE and replayed -- with the library's RCCL communicator
+    the bucket reductions + the optimizer are captured ONCE and replayed -- with the library's RCCL communicator
     (dist.NativeComm) the collectives are stream-ordered launches inside the same graph (a torch.distributed comm is host-scheduled
-    and cannot be captured); per batch only the image, the labels, the plan's index lists and the step's four scalars are copied
-    into their persistent buffers.  Same results as finetune_train_step (tests/test_vcr_gpu.py)."""
+    and cannot be captured); per batch only the engine's device inputs (VCR: the image), the labels, the plan's index lists and the
+    step's four scalars are copied into their persistent buffers.  Same results as finetune_train_step (tests/test_vcr_gpu.py)."""
 
     def __init__(self, state, batch):
         self.state, self.model = state, state._model
@@ -496,24 +540,28 @@ class VCRGraphStep:
         comm = self.model.comm
         assert comm is None or getattr(comm, 'capturable', False), 'only the library RCCL communicator (dist.NativeComm) can be captured'
         finetune_train_step(state, batch)                  # eager step: every buffer and plan capacity exists afterwards
-        self.image_in = torch.zeros_like(batch['image'])
+        self.inputs = [torch.zeros_like(batch[k]) for k in eng.device_keys]
         eng.plan_frozen = True
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
-            eng.forward_device(self.image_in)
+            eng.forward_device(*self.inputs)
             eng.loss_and_grad_logits()
             _backward_reduce_update(state)
 
     def __call__(self, batch, plan=None):
         eng = self.eng
         self.state.prepare_step()
-        self.image_in.copy_(batch['image'], non_blocking=True)
-        eng.set_plan(plan if plan is not None else build_vcr_plan(batch['answers'], eng.d))
-        eng.labels_dev.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(batch['labels']).astype(np.int32).reshape(-1))), non_blocking=True)
+        for buf, k in zip(self.inputs, eng.device_keys):
+            buf.copy_(batch[k], non_blocking=True)
+        eng.upload(batch, plan)
         self.graph.replay()
         self.state.step += 1
         return self.state
+
+
+class VCRGraphStep(FinetuneGraphStep):
+    """The captured VCR step."""
 
 
 def make_vcr_batch(config, B, seed=0, device='cpu'):

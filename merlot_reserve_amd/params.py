@@ -125,6 +125,21 @@ def vcr_param_specs(config):
     return specs
 
 
+def tvqa_param_specs(config):
+    """Parameter tree of MerlotReserveTVQA (finetune/tvqa/tvqa_finetune.py:157-273): the pretraining tree without head / span_encoder
+    (and contrastive_scales, which the finetuning graph never reads), plus proj/kernel [H, 1].  Unlike VCR it keeps audio_encoder.
+    Order = the order backward finishes them: proj, joint tower, token table, audio tower, vision tower."""
+    m = config['model']
+    H = m['hidden_size']
+    vcr = vcr_param_specs(config)
+    cut = next(i for i, s in enumerate(vcr) if s[0].startswith('vision_encoder/'))
+    audio = [('audio_encoder/embedding/kernel', (m['audio_patch_size'], 65, H), (m['audio_patch_size'] * 65, H), 'kernel', 130),
+             ('audio_encoder/embedding/bias', (H,), (H,), 'zeros', None)]
+    audio += _encoder_specs('audio_encoder/transformer', H, m['audio_num_layers'], True)
+    audio += _attnpool_specs('audio_encoder/seq_attnpool', H)
+    return vcr[:cut] + audio + vcr[cut:]
+
+
 def decay_pretrain(flax_shape):
     """pretrain/optimization.py:182-184"""
     return len(flax_shape) > 1

@@ -274,3 +274,61 @@ def build_plan(batch, d, split_from_here, gumbel_z):
     is_v = g >= vis_base
     plan['visT_indptr'], plan['visT_idx'] = csr_from_pairs(g[is_v] - vis_base, jrows[is_v], BG * d.vis_len)
     return plan
+
+
+# ------------------------------------------------------------------------------------------------ the TVQA plan
+def build_tvqa_plan(textonly_seqs, audio_seqs, d):
+    """Every integer decision of MerlotReserveTVQA.__call__ (finetune/tvqa/tvqa_finetune.py:163-258) from `textonly_seqs` and
+    `audio_seqs` [B, A, T, 2] = (token id, segment index) alone; d = tvqa.TVQADims.  The TVQA twin of finetune.build_vcr_plan.
+    Joint sequence q = s*A*B + b*A + a: stream s = 0 audio, 1 text (:242); example-major inside a stream (`.repeat(A, axis=0)`, :179 / :198).
+    Position p < T: the token's embedding -- in the audio stream an AUDIOSPAN position takes an audio row of example b instead (:201-202,
+    modeling.py:685-695); position T + k*V + i: pooled row i of frame k of example b, which carries segment k + 1 (the zero "first image"
+    of :170-224 leaves no other trace)."""
+    A, B, T, V, Sj, n = d.A, d.B, d.T, d.V, d.Sj, d.n
+    AB = A * B
+    aud = np.asarray(audio_seqs).astype(np.int64).reshape(AB, T, 2)
+    txt = np.asarray(textonly_seqs).astype(np.int64).reshape(AB, T, 2)
+    tok = np.concatenate([aud[..., 0], txt[..., 0]], 0)                                             # [n, T]
+    seg = np.concatenate([aud[..., 1], txt[..., 1]], 0)
+    assert tok.min() >= 0 and tok.max() < VOCAB, 'token id out of range'
+    b_of = (np.arange(n) % AB) // A
+    n_audio_rows = d.Na * d.a_tok
+    vis_base = VOCAB + n_audio_rows
+    is_span = tok == AUDIOSPAN
+    is_audio = is_span & (np.arange(n) < AB)[:, None]                                               # the text stream gets no audio_pointers (:183-187)
+    c = np.maximum(np.cumsum(is_span.astype(np.int64), -1) - 1, 0)
+    span, sub = (c // d.a_tok) % d.nspans, c % d.a_tok                                              # :201-202, modeling.py:691
+    acode = VOCAB + (b_of[:, None] * d.nspans + span) * d.a_tok + sub
+    vcode = vis_base + b_of[:, None] * (d.nseg * V) + np.arange(d.nseg * V)[None]
+    gcode = np.concatenate([np.where(is_audio, acode, tok), vcode], 1)                              # [n, Sj]
+    plan = {}
+    plan['joint_gather_indptr'], plan['joint_gather_idx'] = csr_gather(gcode)
+    valid = np.concatenate([tok != PADDING, np.ones((n, d.nseg * V), bool)], 1)                     # modeling.py:726-728; no video-source term
+    plan['joint_code'] = np.where(valid, 0, -1).astype(np.int32).reshape(-1)
+    coords = np.zeros((n, Sj, 4), dtype=np.float64)
+    coords[:, :T, 2] = seg / 16.0
+    coords[:, :T, 3] = (1.0 + np.arange(T, dtype=np.float64))[None] / 1024.0
+    coords[:, T:, :2] = np.tile(rotary_coords_2d(d.gh // d.pr, d.gw // d.pr), [d.nseg, 1])[None]
+    coords[:, T:, 2] = ((1.0 + np.arange(d.nseg)).repeat(V) / 16.0)[None]
+    plan['joint_rot'] = rot_scale_table(coords).reshape(n * Sj, 32)                                 # float32
+    pool_idx = np.argmax((tok == MASK).astype(np.float32), 1)                                       # :250: first MASK, else 0
+    rows = np.arange(n) * Sj + pool_idx
+    plan['pool_indptr'], plan['pool_idx'] = np.arange(n + 1, dtype=np.int32), rows.astype(np.int32)
+    plan['poolT_indptr'], plan['poolT_idx'] = csr_from_pairs(rows, np.arange(n), n * Sj)
+    plan['pool_pos'] = pool_idx.astype(np.int32)
+    # transposes of the gather.  PAD positions carry exactly zero gradient (masked keys, never pooled) unless the pooled position is
+    # itself PAD: that query row attends uniformly to every position, so the whole sequence gets gradient (as in build_vcr_plan)
+    pos_rows = np.arange(n)[:, None] * Sj + np.arange(T)[None]
+    keep = (tok != PADDING) | (tok[np.arange(n), pool_idx] == PADDING)[:, None]
+    keep &= ~is_audio
+    plan['embT_indptr'], plan['embT_idx'] = csr_from_pairs(tok[keep], pos_rows[keep], VOCAB)
+    plan['audT_indptr'], plan['audT_idx'] = csr_from_pairs(acode[is_audio] - VOCAB, pos_rows[is_audio], n_audio_rows)
+    return plan
+
+
+def tvqa_image_transpose(d):
+    """The static transpose of the image part of build_tvqa_plan's gather: pooled image row b*nseg*V + j is read at position T + j
+    by the 2 A sequences of example b, summed in ascending sequence order."""
+    AB, L = d.A * d.B, d.nseg * d.V
+    bb, jj, ss, aa = np.meshgrid(np.arange(d.B), np.arange(L), np.arange(2), np.arange(d.A), indexing='ij')
+    return csr_from_pairs((bb * L + jj).reshape(-1), ((ss * AB + bb * d.A + aa) * d.Sj + d.T + jj).reshape(-1), d.B * L)
