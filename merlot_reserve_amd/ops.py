@@ -36,6 +36,11 @@ GEMM_PROFILE = None
 FAMILY_PROFILE = None
 
 
+def _dense(*tensors):
+    """True when every given tensor (None allowed) is contiguous: what an entry point that takes no leading dimension for it requires."""
+    return all(t is None or t.is_contiguous() for t in tensors)
+
+
 def _timed(family):
     def deco(fn):
         def wrapper(*a, **k):
@@ -391,6 +396,7 @@ def attention_bwd(qkv, code, out, dout, lse, delta, dqkv, rot_tab, nseq, S, nh, 
 def poolattn_fwd(q, k, v, key_rows, out, probs, nh):
     G, R = key_rows.shape
     assert _ld(k) == _ld(v)
+    assert _dense(q, out, key_rows, probs), 'poolattn_fwd: q / out / key_rows / probs carry no leading dimension and must be contiguous'
     if q.dtype == F32:
         check(_lib.load().mr_f32_poolattn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _ld(k), key_rows.data_ptr(), out.data_ptr(),
                                               G, R, nh, _stream()), 'mr_f32_poolattn_fwd')
@@ -404,6 +410,7 @@ def poolattn_fwd(q, k, v, key_rows, out, probs, nh):
 def poolattn_bwd(q, k, v, key_rows, probs, dout, dq, dk, dv, nh):
     G, R = key_rows.shape
     assert _ld(k) == _ld(v) == _ld(dk) == _ld(dv)
+    assert _dense(q, dout, dq, key_rows, probs), 'poolattn_bwd: q / dout / dq / key_rows / probs carry no leading dimension and must be contiguous'
     if q.dtype == F32:
         check(_lib.load().mr_f32_poolattn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _ld(k), key_rows.data_ptr(), dout.data_ptr(),
                                               dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), G, R, nh, _stream()), 'mr_f32_poolattn_bwd')
@@ -459,6 +466,7 @@ def add_rows_periodic(x, table):
 @_timed('rowops')
 def rows_mean_fwd(src, rows, dst):
     G, R = rows.shape
+    assert _dense(dst, rows), 'rows_mean_fwd: dst / rows carry no leading dimension and must be contiguous'
     if src.dtype == F32:
         check(_lib.load().mr_f32_rows_mean_fwd(src.data_ptr(), _ld(src), rows.data_ptr(), dst.data_ptr(), G, R, dst.shape[1],
                                                _stream()), 'mr_f32_rows_mean_fwd')
@@ -471,6 +479,7 @@ def rows_mean_fwd(src, rows, dst):
 @_timed('rowops')
 def rows_mean_bwd(ddst, rows, dsrc):
     G, R = rows.shape
+    assert _dense(ddst, rows), 'rows_mean_bwd: ddst / rows carry no leading dimension and must be contiguous'
     if ddst.dtype == F32:
         check(_lib.load().mr_f32_rows_mean_bwd(ddst.data_ptr(), rows.data_ptr(), dsrc.data_ptr(), _ld(dsrc), G, R, ddst.shape[1], _stream()),
               'mr_f32_rows_mean_bwd')
@@ -511,6 +520,7 @@ def sum_rows_strided(src, ngroups, grp_stride, off, out):
 @_timed('rowops')
 def add_(a, b, y=None):
     y = a if y is None else y
+    assert _dense(a, b, y) and a.numel() == b.numel() == y.numel(), 'add_: flat operands of one size, no leading dimension: they must be contiguous'
     if a.dtype == F32:
         assert y is a
         check(_lib.load().mr_f32_axpby(a.data_ptr(), b.data_ptr(), 1.0, 1.0, a.numel(), _stream()), 'mr_f32_axpby')

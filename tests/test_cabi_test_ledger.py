@@ -10,6 +10,7 @@ from test_cabi_exports import ROOT, declared_symbols
 
 K, F32K, G3, EX, DIRECT = 'test_kernels_gpu.py', 'test_f32_kernels_gpu.py', 'test_gemm3_gpu.py', 'test_gemm_exact_gpu.py', 'test_exports_direct_gpu.py'
 CABI, DIST, REC, RING = 'test_cabi_exports.py', 'test_dist_gpu.py', 'test_records.py', 'test_metrics_ring_gpu.py'
+ROWS = 'test_rowops_exact_gpu.py'           # element-exact: LayerNorm, reductions, row kernels
 
 LEDGER = {
     # library, handles, options
@@ -30,14 +31,14 @@ LEDGER = {
     'mr_gemm_colsum_rows': (('gemm_colsum_job',), (EX, G3, K)),
     'mr_gemm_colsum_supported': (('gemm_colsum_job',), (K,)),
     # LayerNorm, reductions
-    'mr_layernorm_fwd': (('layernorm_fwd',), (K,)),
-    'mr_layernorm_bwd': (('layernorm_bwd',), (K,)),
-    'mr_layernorm_bwd_workspace': (('layernorm_bwd_workspace',), (K,)),
-    'mr_layernorm_bwd_nparts': (('layernorm_bwd',), (K,)),
-    'mr_colsum': (('colsum',), (K,)),
-    'mr_colsum_workspace': (('colsum_workspace',), (K,)),
-    'mr_colsum_nparts': (('colsum',), (K,)),
-    'mr_reduce_partials': (('reduce_partials',), (K,)),
+    'mr_layernorm_fwd': (('layernorm_fwd',), (K, ROWS)),
+    'mr_layernorm_bwd': (('layernorm_bwd',), (K, ROWS)),
+    'mr_layernorm_bwd_workspace': (('layernorm_bwd_workspace',), (K, ROWS)),
+    'mr_layernorm_bwd_nparts': (('layernorm_bwd',), (K, ROWS)),
+    'mr_colsum': (('colsum',), (K, ROWS)),
+    'mr_colsum_workspace': (('colsum_workspace',), (K, ROWS)),
+    'mr_colsum_nparts': (('colsum',), (K, ROWS)),
+    'mr_reduce_partials': (('reduce_partials',), (K, ROWS)),
     # attention
     'mr_attention_fwd': (('attention_fwd',), (K,)),
     'mr_attention_bwd': (('attention_bwd',), (K,)),
@@ -45,18 +46,18 @@ LEDGER = {
     'mr_attention_fwd_dense_mask': (('attention_fwd_dense_mask',), (K,)),
     'mr_attention_bwd_dense_mask': (('attention_bwd_dense_mask',), (K,)),
     'mr_attention_bwd_dense_mask_workspace': (('attention_bwd_dense_mask',), (K,)),
-    'mr_poolattn_fwd': (('poolattn_fwd',), (K,)),
-    'mr_poolattn_bwd': (('poolattn_bwd',), (K,)),
+    'mr_poolattn_fwd': (('poolattn_fwd',), (K, ROWS)),
+    'mr_poolattn_bwd': (('poolattn_bwd',), (K, ROWS)),
     # row operations
-    'mr_segment_sum': (('segment_sum',), (K,)),
-    'mr_rows_mean_fwd': (('rows_mean_fwd',), (K,)),
-    'mr_rows_mean_bwd': (('rows_mean_bwd',), (K,)),
-    'mr_pad_cols': (('pad_cols',), (K,)),
-    'mr_fill_rows': (('fill_rows',), (K,)),
-    'mr_sum_rows_strided': (('sum_rows_strided',), (K,)),
-    'mr_add_bf16': (('add_',), (K,)),
-    'mr_unit_norm_scale_fwd': (('unit_norm_scale_fwd',), (K,)),
-    'mr_unit_norm_scale_bwd': (('unit_norm_scale_bwd',), (K,)),
+    'mr_segment_sum': (('segment_sum',), (K, ROWS)),
+    'mr_rows_mean_fwd': (('rows_mean_fwd',), (K, ROWS)),
+    'mr_rows_mean_bwd': (('rows_mean_bwd',), (K, ROWS)),
+    'mr_pad_cols': (('pad_cols',), (K, ROWS)),
+    'mr_fill_rows': (('fill_rows',), (K, ROWS)),
+    'mr_sum_rows_strided': (('sum_rows_strided',), (K, ROWS)),
+    'mr_add_bf16': (('add_',), (K, ROWS)),
+    'mr_unit_norm_scale_fwd': (('unit_norm_scale_fwd',), (K, ROWS)),
+    'mr_unit_norm_scale_bwd': (('unit_norm_scale_bwd',), (K, ROWS)),
     # losses
     'mr_contrastive_lse': (('contrastive_lse',), (K,)),
     'mr_masked_lm_xent': (('masked_lm_xent',), (DIRECT,)),

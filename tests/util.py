@@ -149,3 +149,95 @@ def same_input_same_bits_report(key, got):
     if not bad.any():
         return ''
     return f'{int(bad.sum())} of {uniq.numel()} distinct pre-activations map to more than one output word, first key {int(uniq[bad][0])}'
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Element-wise checks of the row kernels (tests/test_rowops_exact_gpu.py; tests/test_rowops_exact_checker.py shows that they bite).
+# Where the arithmetic is exact (small integers) the result is compared by bits with exact_report; elsewhere EVERY element must lie inside
+#     |got - ref| <= (2^-8 + 2^-14) |ref| + n_terms 2^-23 mag            (fp32 outputs: 2^-14 in place of 2^-8 + 2^-14)
+# 2^-8 |ref| is one round-to-nearest into bf16.  n 2^-23 mag is twice the worst-case fp32 error of an n-term sum taken in any order (the running
+# error bound: n u sum|term|, u = 2^-24), `mag` being the result's formula in fp64 with every summed term replaced by its absolute value and the
+# error of an earlier sum carried to first order through what follows it.  2^-14 |ref| is 256 fp32 ulps of headroom for rsqrtf / __expf /
+# __logf and the handful of single roundings between the sums.  Both extra terms stay far below one bf16 code.
+def bound_report(got_alloc, ref64, mag64, n_terms, row_index=None, alt_ref64=None):
+    """'' when every stored element of the allocation (rows `row_index`, None: 0..M-1; columns 0..N-1 of ref64 [M, N]) is finite and inside the
+    bound above against ref64 -- or, where given, against alt_ref64 (a second admissible reference: the other side of a rounding boundary
+    that the kernel's intermediate may legitimately fall on) -- and EVERY other cell still holds the sentinel; otherwise what is wrong and where."""
+    assert ref64.dtype == torch.float64 and ref64.dim() == 2
+    M, N = ref64.shape
+    rnd = 2.0 ** -8 + 2.0 ** -14 if got_alloc.element_size() == 2 else 2.0 ** -14
+    bits = as_bits(got_alloc)
+    stored = torch.zeros(bits.shape, dtype=torch.bool, device=bits.device)
+    rows = slice(0, M) if row_index is None else row_index.long()
+    assert row_index is None or row_index.numel() == M
+    stored[rows, :N] = True
+    got = got_alloc[rows, :N].double()
+    noise = n_terms * 2.0 ** -23 * (mag64 + torch.zeros_like(ref64))
+    assert bool((noise >= 0).all())
+
+    def excess(ref):            # error / tolerance; an exact hit of a zero tolerance counts as 0
+        err, tol = (got - ref).abs(), rnd * ref.abs() + noise
+        return torch.where(err <= tol, err / tol.clamp_min(1e-300), torch.full_like(err, float('inf'))).nan_to_num(nan=float('inf'))
+    ex = excess(ref64)
+    if alt_ref64 is not None:
+        ex = torch.minimum(ex, excess(alt_ref64))
+    bad = ~torch.isfinite(got) | (ex > 1)
+    guard_bad = (bits != SENTINEL_BITS[got_alloc.element_size()]) & ~stored
+    msg = []
+    if bad.any():
+        r, c = [int(v) for v in bad.nonzero()[0]]
+        sr = r if row_index is None else int(row_index[r])
+        err = float((got[r, c] - ref64[r, c]).abs())
+        tol = float(rnd * ref64[r, c].abs() + noise[r, c])
+        msg.append(f'{int(bad.sum())} of {M * N} stored elements outside the bound, first at storage row {sr}, column {c}: got {float(got[r, c])!r}, '
+                   f'want {float(ref64[r, c])!r} (error {err:.3e}, tolerance {tol:.3e}); bad rows {int(bad.any(1).sum())}, '
+                   f'bad columns {int(bad.any(0).sum())}')
+    if guard_bad.any():
+        r, c = [int(v) for v in guard_bad.nonzero()[0]]
+        msg.append(f'{int(guard_bad.sum())} guard cells overwritten, first at row {r}, column {c} of the [{got_alloc.shape[0]}, {got_alloc.shape[1]}] allocation')
+    return '; '.join(msg)
+
+
+def bound_margin(got_alloc, ref64, mag64, n_terms, row_index=None):
+    """(worst error / tolerance over the stored elements, worst noise term / rounding term): what a test prints next to its assertion."""
+    M, N = ref64.shape
+    rnd = 2.0 ** -8 + 2.0 ** -14 if got_alloc.element_size() == 2 else 2.0 ** -14
+    got = got_alloc[slice(0, M) if row_index is None else row_index.long(), :N].double()
+    noise = n_terms * 2.0 ** -23 * (mag64 + torch.zeros_like(ref64))
+    tol = rnd * ref64.abs() + noise
+    nz, rz = tol > 0, ref64 != 0
+    return (float(((got - ref64).abs()[nz] / tol[nz]).max()) if nz.any() else 0.0,
+            float((noise[rz] / (rnd * ref64.abs()[rz])).median()) if rz.any() else 0.0)
+
+
+# Integer-valued operands: with every sum of magnitudes <= 256 each fp32 partial sum, in any order, and the bf16 result are exact, so a kernel's
+# output is known to the bit.  The precondition is asserted on the REFERENCE (exact_bf16), never on what a kernel returned.
+def small_ints(shape, k, seed, dtype=torch.bfloat16, device='cpu'):
+    """Uniform integers in [-k, k] (every one a bf16 / fp32 value)."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-k, k + 1, shape, generator=g).to(dtype).to(device)
+
+
+def sparse_int_rows(rows, cols, seed, dtype=torch.bfloat16, device='cpu'):
+    """Integers [rows, cols] whose column sums are exact in any order -- sum |x| <= 256 in every column -- and in which EVERY row has a non-zero
+    entry, so that a dropped or doubled row changes a column sum.  Up to 256 rows the matrix is dense; beyond, row r holds one entry in column r % cols."""
+    g = torch.Generator().manual_seed(seed)
+    per_col = (rows + cols - 1) // cols
+    if rows <= 256:
+        k = min(3, 256 // rows)
+        x = torch.randint(-k, k + 1, (rows, cols), generator=g)
+    else:
+        k = min(3, 256 // per_col)
+        assert k >= 1, f'{rows} rows need more than {cols} columns'
+        x = torch.zeros(rows, cols, dtype=torch.int64)
+    r = torch.arange(rows)
+    x[r, r % cols] = torch.randint(1, k + 1, (rows,), generator=g) * (2 * torch.randint(0, 2, (rows,), generator=g) - 1)
+    assert int(x.abs().sum(0).max()) <= 256 and bool((x != 0).any(1).all())
+    return x.to(dtype).to(device)
+
+
+def exact_bf16(ref64):
+    """The fp64 reference as bf16, after asserting that nothing is lost: every value is a bf16 value (an integer of magnitude <= 256 is one)."""
+    out = ref64.to(torch.bfloat16)
+    assert torch.equal(out.double(), ref64), 'the reference is not exactly representable in bf16: the test data break the precondition'
+    return out
