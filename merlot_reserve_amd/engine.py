@@ -21,6 +21,12 @@ from .planner import VOCAB, build_plan, static_tables
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 
+def side_stream_disabled():
+    """MR_NO_SIDE_STREAM=1, read when the work is issued (bench.py sets and clears it between steps of one process for its exclusive
+    timing pass): the side stream's work is issued in line on the current stream."""
+    return os.environ.get('MR_NO_SIDE_STREAM') == '1'
+
+
 class TowerState:
     """Saved activations of one TransformerEncoder (modeling.py:283-376) over M = nseq*S rows."""
 
@@ -44,7 +50,8 @@ class TowerEngine:
     """What every program built from TransformerEncoder towers shares (pretraining step, VCR finetuning step): the
     encoder forward / hand-written backward over a TowerState, the CLS head + attention pool of the vision / audio
     towers, the two scratch sets (main / side stream) and the device copies of the per-batch plan.
-    Subclasses set: self.p (ParamStore), self.W (weight views), self.dev, self.dtype, self.fwd_only, self.side_stream,
+    Subclasses set: self.p (ParamStore), self.W / self.G (weight / gradient views), self.dev, self.dtype, self.fwd_only, self.side_stream,
+    self.tables (static device tables: '{vit,audio}_rot', '{vit,audio}_pool_rows' of the towers the program has),
     self.sc_main / self.sc_side / self.cur (via _make_scratch), self.plan_dev / _plan_caps / _plan_views / plan_frozen."""
 
     def _make_scratch(self, Ms, Gs, Ps, H, nh):
@@ -100,10 +107,12 @@ class TowerEngine:
     def fgemm(self, a, name, out, **kw):
         """Forward Dense: out = a @ W[name].  The bf16 program reads the TRANSPOSED working copy where the store keeps one
         (params.ParamStore.wT): both operands contraction-contiguous, the fast GEMM path; same values, same result."""
+        b, transB = self._fweight(name)
+        return self.gemm(a, b, out, transB=transB, **kw)
+
+    def _fweight(self, name):
         wT = getattr(self.p, 'wT', None) if self.dtype == BF16 else None
-        if wT and name in wT and os.environ.get('MR_NO_WT') != '1':
-            return self.gemm(a, wT[name], out, transB=True, **kw)
-        return self.gemm(a, self.W[name], out, **kw)
+        return (wT[name], True) if wT and name in wT else (self.W[name], False)
 
     def gemm_args(self, a, b, out, **kw):
         return ops.gemm_args(a, b, out, ws=None if self.cur is None else self.cur.gemm_ws, **kw)
@@ -111,24 +120,20 @@ class TowerEngine:
     def fgemm_grouped(self, items):
         """Several independent forward Dense layers [(a, weight name, out, kwargs)] in one mr_gemm_grouped call (small problems of one
         operand layout share a launch; anything else falls back to one launch each inside the library)."""
-        wT = getattr(self.p, 'wT', None) if self.dtype == BF16 else None
-        if self.dtype != BF16 or os.environ.get('MR_NO_SMALL_GROUPING') == '1':
+        if self.dtype != BF16:
             for a, name, out, kw in items:
                 self.fgemm(a, name, out, **kw)
             return
         args = []
         for a, name, out, kw in items:
-            if wT and name in wT and os.environ.get('MR_NO_WT') != '1':
-                args.append(self.gemm_args(a, wT[name], out, transB=True, **kw))
-            else:
-                args.append(self.gemm_args(a, self.W[name], out, **kw))
+            b, transB = self._fweight(name)
+            args.append(self.gemm_args(a, b, out, transB=transB, **kw))
         ops.gemm_grouped(args)
 
     # tower-level deferred reductions: between _begin_tower_reductions() and _flush_tower_reductions() every LayerNorm /
     # colsum issued through _t_ln_bwd / _t_colsum leaves its partial rows in a workspace of its own
     def _begin_tower_reductions(self):
-        off = os.environ.get('MR_NO_BATCH_REDUCE') == '1' or os.environ.get('MR_NO_TOWER_DEFER') == '1' or self.dtype == F32   # (A/B switches; fp32: immediate)
-        return {'jobs': None if off else [], 'ln': 0, 'cs': 0, 'sc': self.cur}
+        return {'jobs': None if self.dtype == F32 else [], 'ln': 0, 'cs': 0, 'sc': self.cur}      # (fp32: immediate)
 
     def _t_ln_bwd(self, tr, *a, **k):
         if tr is None or tr['jobs'] is None:
@@ -150,25 +155,16 @@ class TowerEngine:
 
     def _on_side(self, fn):
         """Issue fn()'s kernels on the side stream (forked from / joined to the current stream by the caller)."""
-        if self.fwd_only:
-            if os.environ.get('MR_NO_SIDE_STREAM') == '1':
-                return fn()
-            with torch.cuda.stream(self.side_stream):
-                return fn()
-        self.cur = self.sc_side
-        side_cus = int(os.environ.get('MR_SIDE_CUS', '0'))       # (experiment) persistent GEMM grids of the side stream's tower
-        prev = ops.get_option('gemm_cus') if side_cus else 0
+        if not self.fwd_only:
+            self.cur = self.sc_side
         try:
-            if side_cus:
-                ops.set_option('gemm_cus', side_cus)
-            if os.environ.get('MR_NO_SIDE_STREAM') == '1':       # (A/B switch) same work, issued in line
+            if side_stream_disabled():       # same work, issued in line
                 return fn()
             with torch.cuda.stream(self.side_stream):
                 return fn()
         finally:
-            if side_cus:
-                ops.set_option('gemm_cus', prev)
-            self.cur = self.sc_main
+            if not self.fwd_only:
+                self.cur = self.sc_main
 
     def _unpad_csr(self, nseq, S):
         rows = (np.arange(nseq)[:, None] * S + 1 + np.arange(S - 1)[None]).reshape(-1).astype(np.int32)
@@ -263,13 +259,13 @@ class TowerEngine:
         2 layers = 216 (one round at 84 %; 3 or 4 layers are no better); large: 192 per layer -> 4 layers = 768 = three full rounds
         (one layer per launch left a quarter of the chip idle: 24 rounds per tower instead of 18).  K = M tokens must be long
         enough to amortise a tile's prologue."""
-        if os.environ.get('MR_WGRAD_PAIR') == '0' or M < 2048:
+        if M < 2048:
             return 1
         t = lambda m, n: ((m + 255) // 256) * ((n + 255) // 256)
         tiles = t(4 * H, H) + t(H, 4 * H) + t(H, H) + t(H, 3 * H)
         eff = lambda n: n / (((n + 255) // 256) * 256)
         best = 1
-        for g in range(2, int(os.environ.get('MR_WGRAD_MAX', '4')) + 1):
+        for g in range(2, 5):
             if eff(g * tiles) > eff(best * tiles) + 0.05:
                 best = g
         return best
@@ -298,7 +294,7 @@ class TowerEngine:
             tiles = group * (t256(4 * H, H) + t256(H, 4 * H) + t256(H, H) + t256(H, 3 * H))
             extra = sum(t256(x.shape[1], dy.shape[1]) for x, dy, _ in extra_wgrads)
             rounds = lambda n: (n + 255) // 256
-            if M >= 2048 and 4 * group + len(extra_wgrads) <= 20 and rounds(tiles + extra) == rounds(tiles) and os.environ.get('MR_NO_WGRAD_EXTRA') != '1':
+            if M >= 2048 and 4 * group + len(extra_wgrads) <= 20 and rounds(tiles + extra) == rounds(tiles):
                 pending += [self.gemm_args(x, dy, out, transA=True) for x, dy, out in extra_wgrads]
             else:
                 for x, dy, out in extra_wgrads:
@@ -309,20 +305,19 @@ class TowerEngine:
         # everything above the layers (heads, pooling, final LayerNorm) is reduced here: a data-parallel trainer hands the
         # tower's LAST layers' gradient bucket -- which holds these leaves -- to the all-reduce at the first layer_done
         self._flush_tower_reductions(tr)
-        jobs = None if os.environ.get('MR_NO_BATCH_REDUCE') == '1' or self.dtype == F32 else []      # (A/B switch) immediate reductions
+        jobs = None if self.dtype == F32 else []      # (fp32: immediate reductions)
         for l in reversed(range(st.L)):
             n = self._names(prefix, l)
             T_q, T_h = T_qs[len(done_layers)], T_hs[len(done_layers)]
             Dmid, Dnext = free.pop(), free.pop()
             gi = len(done_layers)               # position in the weight-gradient group: its own partial-row workspaces
-            fused_bb1 = ops.gemm_colsum_job(Dcur, W[n['w2']], T_h, self.cur.cs_fused[gi], G[n['bb1']],
-                                            jobs if os.environ.get('MR_NO_GEMM_COLSUM') != '1' else None, transB=True,
+            fused_bb1 = ops.gemm_colsum_job(Dcur, W[n['w2']], T_h, self.cur.cs_fused[gi], G[n['bb1']], jobs, transB=True,
                                             aux=st.hpre[l], ws=self.cur.gemm_ws)            # d hpre (+ its column sums = d bias)
             self.gemm(T_h, W[n['w1']], T_a, transB=True)                                    # d ln2
             ops.layernorm_bwd(T_a, st.xmid[l], W[n['g2']], st.stats[2 + 2 * l, 0], st.stats[2 + 2 * l, 1], Dmid,
                               G[n['g2']], G[n['b2']], self.cur.ln_wsA[gi], dx_add=Dcur, jobs=jobs)    # Dmid = d xmid
             self.gemm(Dmid, W[n['wo']], T_a, transB=True)                                   # d att
-            fuse_q = jobs is not None and os.environ.get('MR_NO_ATTN_COLSUM') != '1' and dense_mask is None          # (A/B switch)
+            fuse_q = jobs is not None and dense_mask is None
             if dense_mask is not None:       # any mask (the forward ran mr_attention_fwd_dense_mask): the plain backward pair; d bias = a column-sum pass below
                 ops.attention_bwd_dense_mask(st.qkv[l], dense_mask, T_a, T_q, rot, st.nseq, st.S, nh)
             else:
@@ -384,7 +379,7 @@ class TowerEngine:
         # the small weight gradients of the head (pool out / query projections, cls_proj: K = 1152 / 1152 / 64 rows) feed nothing in this
         # backward: they leave the chain of data gradients and run as ONE grouped launch at its end
         small_wgrads = []
-        defer = self.dtype == BF16 and os.environ.get('MR_NO_SMALL_GROUPING') != '1'
+        defer = self.dtype == BF16
 
         def wgrad(x, dy, out):
             if defer:
@@ -417,6 +412,30 @@ class TowerEngine:
         ops.sum_rows_strided(D, st.nseq, st.S, 0, G[f'{prefix_t}/cls'])
         return D
 
+    # ------------------------------------------------------------------------------------------ input-tower backward stages
+    def backward_stage_audio(self):
+        d, G, ta, t = self.d, self.G, self.ta, self.tables
+        tr = self._begin_tower_reductions()
+        Da = self._tower_with_pool_backward(ta, 'audio_encoder/transformer', 'audio_encoder/seq_attnpool', t['audio_rot'],
+                                            t['audio_pool_rows'], self.a_qin, self.a_q, self.a_k, self.a_v, self.a_po,
+                                            self.a_probs, self.d_audio_seq, self.d_a_cls, self.Da, tr=tr)
+        Dp = self.cur.Dpatch[:d.Na * d.a_len]
+        ops.segment_sum([Da], self.unpad_a[0], self.unpad_a[1], Dp)
+        self._t_colsum(tr, Dp, G['audio_encoder/embedding/bias'])
+        self._flush_tower_reductions(tr)
+        self.gemm(self._audio2d, Dp, G['audio_encoder/embedding/kernel'], transA=True)
+
+    def backward_stage_vision(self, layer_done=None):
+        d, G, tv, t = self.d, self.G, self.tv, self.tables
+        tr = self._begin_tower_reductions()
+        Dv = self._tower_with_pool_backward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', t['vit_rot'],
+                                            t['vit_pool_rows'], self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po,
+                                            self.v_probs, self.d_imgs_seq, self.d_v_cls, self.Dv, layer_done=layer_done, tr=tr)
+        Dp = self.cur.Dpatch[:d.Nv * d.hw]
+        ops.segment_sum([Dv], self.unpad_v[0], self.unpad_v[1], Dp)
+        self._t_colsum(tr, Dp, G['vision_encoder/embedding/bias'])
+        self._flush_tower_reductions(tr)
+        self.gemm(self._images2d, Dp, G['vision_encoder/embedding/kernel'], transA=True)
 
 
 class PretrainEngine(TowerEngine):
@@ -654,7 +673,7 @@ class PretrainEngine(TowerEngine):
         self.diag.zero_()
         # The six (objective, direction) problems are independent: each of the three products runs as ONE grouped launch over all of
         # them (bf16 program; alone, every one of these 18 GEMMs is a 17-23 us latency chain of k-tiles on one or two workgroups).
-        grouped = not self.fwd_only and self.dtype == BF16 and os.environ.get('MR_NO_LOSS_GROUPING') != '1'
+        grouped = not self.fwd_only and self.dtype == BF16
         qs = [self.E[p['q_off']:p['q_off'] + p['Lq']] for p in self.cprob]
         if grouped:
             ops.gemm_grouped([self.gemm_args(q, self.Kcat[p['kb']:p['kb'] + p['V']], p['logits'], transB=True) for p, q in zip(self.cprob, qs)])
@@ -763,31 +782,6 @@ class PretrainEngine(TowerEngine):
         if d.no_vision:                  # d(imgs_seq * 0) = 0
             self.d_imgs_seq.zero_()
         ops.segment_sum([self.d_acls_g], self._pl('aclsT_indptr'), self._pl('aclsT_idx'), self.d_a_cls)
-
-    def backward_stage_audio(self):
-        d, W, G, H = self.d, self.W, self.G, self.d.H
-        ta = self.ta
-        tr = self._begin_tower_reductions()
-        Da = self._tower_with_pool_backward(ta, 'audio_encoder/transformer', 'audio_encoder/seq_attnpool', self.tables['audio_rot'],
-                                            self.tables['audio_pool_rows'], self.a_qin, self.a_q, self.a_k, self.a_v, self.a_po,
-                                            self.a_probs, self.d_audio_seq, self.d_a_cls, self.Da, tr=tr)
-        Dp = self.cur.Dpatch[:d.Na * d.a_len]
-        ops.segment_sum([Da], self.unpad_a[0], self.unpad_a[1], Dp)
-        self._t_colsum(tr, Dp, G['audio_encoder/embedding/bias'])
-        self._flush_tower_reductions(tr)
-        self.gemm(self._audio2d, Dp, G['audio_encoder/embedding/kernel'], transA=True)
-    def backward_stage_vision(self, layer_done=None):
-        d, W, G, H = self.d, self.W, self.G, self.d.H
-        tv = self.tv
-        tr = self._begin_tower_reductions()
-        Dv = self._tower_with_pool_backward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.tables['vit_rot'],
-                                            self.tables['vit_pool_rows'], self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po,
-                                            self.v_probs, self.d_imgs_seq, self.d_v_cls, self.Dv, layer_done=layer_done, tr=tr)
-        Dp = self.cur.Dpatch[:d.Nv * d.hw]
-        ops.segment_sum([Dv], self.unpad_v[0], self.unpad_v[1], Dp)
-        self._t_colsum(tr, Dp, G['vision_encoder/embedding/bias'])
-        self._flush_tower_reductions(tr)
-        self.gemm(self._images2d, Dp, G['vision_encoder/embedding/kernel'], transA=True)
 
     def loss_info(self):
         """Host dict like the reference's loss_info (pretrain_model.py:263-303) from the device accumulators."""

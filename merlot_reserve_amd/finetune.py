@@ -31,18 +31,9 @@ import torch
 
 from . import ops
 from .engine import BF16, F32, I32, TowerEngine, TowerState
+from .optim import AdamStepState, BucketSchedule, lr_scale_linearwarmup_lineardecay, vision_cut_buckets
 from .params import VOCAB, ParamStore, decay_finetune, vcr_param_specs
 from .planner import MASK, PADDING, csr_from_pairs, csr_gather, rot_scale_table, rotary_coords_2d
-
-
-def lr_scale_linearwarmup_lineardecay(step, num_warmup_steps, num_train_steps):
-    """pretrain/optimization.py:140-155 in float32"""
-    f = np.float32
-    step = f(step)
-    if step < num_warmup_steps:
-        return float(step / f(num_warmup_steps))
-    post = (step - f(num_warmup_steps)) / f(num_train_steps - num_warmup_steps + 1.0)
-    return float(f(1.0) - min(post, f(1.0)))
 
 
 class VCRDims:
@@ -93,7 +84,7 @@ class FinetuneEngine(TowerEngine):
     asks of an engine.  A subclass sets: metric_names (the keys of loss_info()), device_keys (the batch entries that live on the device, in
     the order forward_device takes them), batch_size / slice_example (the size of a batch and one example of it), build_plan,
     forward_device, loss_and_grad_logits, backward_stages (the third field of a stage marks the vision tower's: the only one whose layers
-    are cut into ('vision', l) buckets), gradient_buckets; and the buffers named below."""
+    are cut into ('vision', l) buckets), head_buckets; and the buffers named below."""
 
     def _idx_capacity(self):
         return self.tj.M + 64
@@ -111,32 +102,17 @@ class FinetuneEngine(TowerEngine):
         for stage, _key, _cuts in self.backward_stages():
             stage()
 
-    def _buckets_with_vision_cuts(self, head):
-        """`head` (the buckets in front of the vision tower) + the vision tower cut at 2/3 and 1/3 of its depth + 'vision_end' = the rest."""
-        p, Lv = self.p, self.d.Lv
-        v0, v1 = p.tower_ranges['vision_encoder']
-        assert v1 == p.total and head[-1][2] == v0
-        cuts = sorted({l for l in (Lv - Lv // 3, Lv - 2 * (Lv // 3)) if 0 < l < Lv}, reverse=True)
-        lo_of = lambda l: p.offsets[f'vision_encoder/transformer/layer_{l:02d}/pre_attn_ln/scale'][0]
-        buckets, hi = list(head), v1
-        for l in cuts:
-            buckets.append((('vision', l), lo_of(l), hi))
-            hi = lo_of(l)
-        buckets.append(('vision_end', v0, hi))
-        assert sum(b[2] - b[1] for b in buckets) == p.total and all(b[1] % 2048 == 0 and b[2] % 2048 == 0 for b in buckets)
-        return buckets, cuts
+    def gradient_buckets(self):
+        """(buckets, vision cuts): ranges of the flat gradient buffer in the order backward makes them final -- the subclass's
+        head_buckets(), then the vision tower cut at 2/3 and 1/3 of its depth and 'vision_end' = the rest (optim.vision_cut_buckets)."""
+        return vision_cut_buckets(self.p, self.d.Lv, self.head_buckets())
 
-    def backward_stage_vision(self, layer_done=None):
-        d, G, tv = self.d, self.p.g, self.tv
-        tr = self._begin_tower_reductions()
-        Dv = self._tower_with_pool_backward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.vit_rot, self.vit_pool_rows,
-                                            self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po, self.v_probs, self.d_imgs_seq,
-                                            self.d_v_cls, self.Dv, layer_done=layer_done, tr=tr)
-        Dp = self.cur.Dpatch[:d.Nv * d.hw]
-        ops.segment_sum([Dv], self.unpad_v[0], self.unpad_v[1], Dp)
-        self._t_colsum(tr, Dp, G['vision_encoder/embedding/bias'])
-        self._flush_tower_reductions(tr)
-        self.gemm(self._images2d, Dp, G['vision_encoder/embedding/kernel'], transA=True)
+    def _backward_proj_head(self):
+        """Backward of the Dense(1) head and of the pooling: d proj, d pooled_h, and self.Dj = zero except the pooled rows."""
+        dl = self.dlogits[:, :1]
+        self.gemm(dl, self.pooled_h, self.G['proj/kernel'], transA=True)              # d proj [1, H] = dlogits^T . pooled_h
+        self.gemm(dl, self.W['proj/kernel'], self.d_pooled)                           # d pooled_h = dlogits . proj^T
+        ops.segment_sum([self.d_pooled], self._pl('poolT_indptr'), self._pl('poolT_idx'), self.Dj)   # zero except the pooled rows
 
 
 class VCREngine(FinetuneEngine):
@@ -162,10 +138,11 @@ class VCREngine(FinetuneEngine):
         self.tj = TowerState(d.n * d.Sj, H, d.Lj, d.n, d.Sj, dev)
         # static tables: ViT rotary / pool rows; joint rotary (text: segment 0, token index 1..T; vision: pooled-grid (h, w),
         # segment 0 -- identical for every sequence: M:697-720 with token_segment_idx = 0, F:161)
-        self.vit_rot = torch.from_numpy(rot_scale_table(np.concatenate([np.zeros((1, 2)), rotary_coords_2d(d.gh, d.gw)], 0))).to(dev)
+        vit_rot = torch.from_numpy(rot_scale_table(np.concatenate([np.zeros((1, 2)), rotary_coords_2d(d.gh, d.gw)], 0))).to(dev)
         pr, h2, w2 = d.pr, d.gh // d.pr, d.gw // d.pr
         n_, i2, j2, di, dj = np.meshgrid(np.arange(B), np.arange(h2), np.arange(w2), np.arange(pr), np.arange(pr), indexing='ij')
-        self.vit_pool_rows = torch.from_numpy((n_ * d.Sv + 1 + (i2 * pr + di) * d.gw + j2 * pr + dj).reshape(B * h2 * w2, pr * pr).astype(np.int32)).to(dev)
+        vit_pool_rows = torch.from_numpy((n_ * d.Sv + 1 + (i2 * pr + di) * d.gw + j2 * pr + dj).reshape(B * h2 * w2, pr * pr).astype(np.int32)).to(dev)
+        self.tables = {'vit_rot': vit_rot, 'vit_pool_rows': vit_pool_rows}
         coords = np.zeros((d.Sj, 4))
         coords[:d.T, 3] = (1.0 + np.arange(d.T)) / 1024.0
         coords[d.T:, :2] = rotary_coords_2d(h2, w2)
@@ -201,7 +178,7 @@ class VCREngine(FinetuneEngine):
         d, W, tv, tj = self.d, self.W, self.tv, self.tj
         self._images2d = image.reshape(d.B * d.hw, d.pp3)
         self.fgemm(self._images2d, 'vision_encoder/embedding/kernel', tv.xin, bias=W['vision_encoder/embedding/bias'], row_map=(d.hw, d.Sv, 1))
-        self._tower_with_pool_forward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.vit_rot, self.vit_pool_rows,
+        self._tower_with_pool_forward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.tables['vit_rot'], self.tables['vit_pool_rows'],
                                       self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po, self.v_probs, self.imgs_seq, self.v_cls)
         ops.segment_sum([W['token_encoder/Embed_0/embedding'], self.imgs_seq], self._pl('joint_gather_indptr'), self._pl('joint_gather_idx'), tj.xin)
         self.encoder_forward(tj, 'joint_transformer', self.joint_rot, self._pl('joint_code'))
@@ -218,20 +195,16 @@ class VCREngine(FinetuneEngine):
 
     def backward_stages(self):
         """[(stage, the bucket of gradient_buckets() that is final after it, whether it is the VISION tower's stage: that one takes
-        layer_done and the step hands over the ('vision', l) buckets of _buckets_with_vision_cuts from it)]"""
+        layer_done and the step hands over the ('vision', l) buckets of gradient_buckets() from it)]"""
         return [(self.backward_stage_joint, 'joint', False), (self.backward_stage_vision, 'vision_end', True)]
 
-    def gradient_buckets(self):
-        """Ranges of the flat gradient buffer in the order backward makes them final (like trainer.Trainer._make_buckets):
-        'joint' = [proj, joint tower, token table]; the vision tower cut at 2/3 and 1/3 of its depth; 'vision_end' = the rest."""
-        return self._buckets_with_vision_cuts([('joint', 0, self.p.tower_ranges['vision_encoder'][0])])
+    def head_buckets(self):
+        """'joint' = [proj, joint tower, token table]"""
+        return [('joint', 0, self.p.tower_ranges['vision_encoder'][0])]
 
     def backward_stage_joint(self):
-        d, W, G, tj = self.d, self.W, self.p.g, self.tj
-        dl = self.dlogits[:, :1]
-        self.gemm(dl, self.pooled_h, G['proj/kernel'], transA=True)                   # d proj [1, H] = dlogits^T . pooled_h
-        self.gemm(dl, W['proj/kernel'], self.d_pooled)                                # d pooled_h = dlogits . proj^T
-        ops.segment_sum([self.d_pooled], self._pl('poolT_indptr'), self._pl('poolT_idx'), self.Dj)   # zero except the pooled rows
+        G, tj = self.G, self.tj
+        self._backward_proj_head()
         # the tower-level reductions (final / pre LayerNorm) are deferred into ONE mr_reduce_partials launch each side of the layers, as in
         # the pretraining engine (they were two-level immediate reductions here: 19 launches of ~68 us per VCR step, round-3 profile)
         tr = self._begin_tower_reductions()
@@ -264,8 +237,13 @@ class MerlotReserveVCR:
         """shard_optimizer = True: the Adam moments are partitioned over the ranks of `comm` (FO:148-171; zero.py)."""
         self.config, self.device, self.rank, self.world, self.comm, self.seed = config, torch.device(device), rank, world, comm, seed
         self.params_store, self.engine, self._last_tree = None, None, None
-        self.shard_optimizer, self.shards = shard_optimizer, None
+        self.shard_optimizer, self._train_state = shard_optimizer, None      # (the FinetuneTrainState built on this model last)
         assert not shard_optimizer or comm is not None, 'shard_optimizer needs a communicator (its world may be 1)'
+
+    @property
+    def shards(self):
+        """zero.MomentShards of a model built with shard_optimizer=True, once it has a train state (which owns them)."""
+        return None if self._train_state is None else self._train_state.shards
 
     @classmethod
     def from_config(cls, config, **kwargs):
@@ -279,9 +257,6 @@ class MerlotReserveVCR:
             self.params_store = ParamStore(self.config, self.device, seed=self.seed, specs=self.param_specs(self.config),
                                            decay_rule=decay_finetune, with_orig=True, with_optimizer=not self.shard_optimizer)
             self.engine = self.engine_cls(self.config, B, self.params_store, self.device)
-            if self.shard_optimizer:
-                from .zero import MomentShards
-                self.shards = MomentShards(self.params_store, self.engine.gradient_buckets()[0], self.comm)
         elif self.engine.d.B != B:
             raise ValueError(f'this model was initialised for {self.engine.d.B} examples per device, got {B}')
         return self.engine
@@ -309,109 +284,58 @@ class MerlotReserveVCR:
         return self.apply(None, batch)
 
 
-class FinetuneTrainState:
+class FinetuneTrainState(AdamStepState):
+    """FO:77-90: the bf16 Adam with bias correction, subtract_old_weights decay (the store's `orig`) and the linear schedule."""
+    eps = 1e-6
+    bias_correction = True
+
     def __init__(self, model, opt_config):
-        self._model, self.opt_config, self.step = model, dict(opt_config), 0
-        self.apply_fn = model.apply
+        super().__init__(model.params_store, opt_config)
+        self._model, self.apply_fn = model, model.apply
+        if model.shard_optimizer:        # the model's moments exist once: a later state on the same model takes them over, as it does p.mu / p.nu
+            from .zero import MomentShards
+            self.shards = model.shards or MomentShards(self.store, model.engine.gradient_buckets()[0], model.comm)
+        model._train_state = self
 
     @property
     def params(self):
-        return self._model.params_store.master_tree()
+        return self.store.master_tree()
 
-    def _scalars(self):
+    def _schedule(self):
         oc = self.opt_config
-        assert oc.get('use_bfloat16_adam', True)
-        sched = lr_scale_linearwarmup_lineardecay(self.step, oc['num_warmup_steps'], oc['num_train_steps'])
-        b1, b2 = oc.get('beta_1', 0.9), oc.get('beta_2', 0.98)
-        bc1 = bc2 = 1.0
-        if oc.get('do_bias_correction', True):
-            bc1, bc2 = 1.0 - b1 ** (self.step + 1), 1.0 - b2 ** (self.step + 1)
-        return sched, -oc['learning_rate'], bc1, bc2
+        return lr_scale_linearwarmup_lineardecay(self.step, oc['num_warmup_steps'], oc['num_train_steps'])
+
+    def _host_update(self, sched, neg_lr, bc1, bc2):
+        p = self.store
+        ops.adam_bf16_update_finetune(p.master, p.work, p.grad, p.mu, p.nu, p.orig, p.decay_flags, *self._adam_args(), sched, neg_lr, bc1, bc2)
 
     def apply_gradients(self):
-        """FO:77-90 + apply_updates, one fused launch over the flat buffers."""
-        oc, p = self.opt_config, self._model.params_store
-        if self._model.shards is not None:        # partitioned moments: bucket by bucket, each rank its chunk; a COLLECTIVE
-            self.prepare_step()
-            for key in self._model.shards.table:
-                self._model.shards.update(key, self.apply_shard)
-            self.step += 1
-            return self
-        sched, neg_lr, bc1, bc2 = self._scalars()
-        ops.adam_bf16_update_finetune(p.master, p.work, p.grad, p.mu, p.nu, p.orig, p.decay_flags, oc.get('beta_1', 0.9), oc.get('beta_2', 0.98),
-                                      oc.get('eps', 1e-6), oc['weight_decay_rate'], sched, neg_lr, bc1, bc2)
-        p.update_transposed()
-        self.step += 1
+        """FO:77-90 + apply_updates."""
+        super().apply_gradients()
         return self
-
-    # ---- the same update per gradient bucket with the step's scalars in a device vector, so that the launches can sit inside a
-    # hipGraph and overlap the rest of backward (like trainer.TrainState.prepare_step / apply_range)
-    def prepare_step(self):
-        dev = self._model.params_store.device
-        if getattr(self, 'hyper', None) is None:
-            self.hyper = torch.zeros(4, dtype=torch.float32, device=dev)
-            self._hyper_host = [torch.zeros(4, dtype=torch.float32, pin_memory=dev.type == 'cuda') for _ in range(2)]
-            self._hyper_ev, self._hyper_turn = [None, None], 0
-        i = self._hyper_turn
-        self._hyper_turn ^= 1
-        if self._hyper_ev[i] is not None:
-            self._hyper_ev[i].synchronize()
-        sched, neg_lr, bc1, bc2 = self._scalars()
-        f32 = np.float32         # 1 / bias_correction in fp32, as mr_adam_bf16_update_finetune forms it from its float arguments
-        self._hyper_host[i].copy_(torch.tensor([sched, neg_lr, float(f32(1.0) / f32(bc1)), float(f32(1.0) / f32(bc2))], dtype=torch.float32))
-        self.hyper.copy_(self._hyper_host[i], non_blocking=True)
-        if dev.type == 'cuda':
-            self._hyper_ev[i] = torch.cuda.Event()
-            self._hyper_ev[i].record()
-
-    def apply_range(self, lo, hi, mu=None, nu=None, transposed=True):
-        oc, p = self.opt_config, self._model.params_store
-        ops.adam_bf16_update_dev(p.master[lo:hi], p.work[lo:hi], p.grad[lo:hi], p.mu[lo:hi] if mu is None else mu, p.nu[lo:hi] if nu is None else nu,
-                                 p.orig[lo:hi], p.decay_flags[lo // 2048:hi // 2048], oc.get('beta_1', 0.9), oc.get('beta_2', 0.98), oc.get('eps', 1e-6),
-                                 oc['weight_decay_rate'], self.hyper)
-        if transposed:
-            p.update_transposed(lo, hi)
-
-    def apply_shard(self, lo, hi, mu, nu):
-        self.apply_range(lo, hi, mu=mu, nu=nu, transposed=False)
 
     # ---- checkpoint form: flax `to_state_dict` of the finetuning chain (finetune/optimization.py:77-90): '0' = the bf16 Adam state
     # {count, mu, nu}, '1' = subtract_old_weights' orig_params (bf16), '2' = add_decayed_weights (empty), '3' = the schedule's count,
     # '4' = scale (empty).  (The reference notes that ITS finetuning state cannot be restarted; this one can.)  With partitioned
     # moments (shard_optimizer=True) state_dict() gathers them from every rank: a COLLECTIVE, see checkpoint.save_checkpoint(rank=).
     def state_dict(self):
-        m, p = self._model, self._model.params_store
-        mu, nu = (p.mu, p.nu) if m.shards is None else m.shards.full_moments()
+        p = self.store
+        mu, nu = self._moments()
         count = torch.tensor(self.step, dtype=torch.int32)
         return {'step': self.step, 'params': p.master_tree(),
                 'opt_state': {'0': {'count': count, 'mu': p._to_tree(mu), 'nu': p._to_tree(nu)}, '1': {'orig_params': p._to_tree(p.orig)},
                               '2': {}, '3': {'count': count.clone()}, '4': {}}}
 
     def load_state_dict(self, sd):
-        m, p = self._model, self._model.params_store
+        p = self.store
         p.load_tree(sd['params'])
         self.step = int(sd.get('step', 0))
         opt = sd.get('opt_state')
         if not opt:
             return self
-
-        def flat(tree):
-            host = torch.zeros(p.total, dtype=torch.bfloat16)
-            for name, *_ in p.specs:
-                o, n = p.offsets[name]
-                leaf = tree
-                for k in name.split('/'):
-                    leaf = leaf[k]
-                host[o:o + n] = leaf.reshape(-1).to(torch.bfloat16)
-            return host
-        mu, nu = flat(opt['0']['mu']), flat(opt['0']['nu'])
-        if m.shards is None:
-            p.mu.copy_(mu)
-            p.nu.copy_(nu)
-        else:
-            m.shards.store_moments(mu.to(p.device), nu.to(p.device))
+        self._load_moments(opt['0']['mu'], opt['0']['nu'])
         if opt.get('1') and 'orig_params' in opt['1']:
-            p.orig.copy_(flat(opt['1']['orig_params']))
+            p.orig.copy_(self._flat_bf16(opt['1']['orig_params']))
         return self
 
 
@@ -435,43 +359,29 @@ def train_loss_fn(state, params, batch):
 
 
 def _backward_reduce_update(state):
-    """Backward from the engine's dlogits with every finished gradient BUCKET handed to a second stream: nan_to_num ->
-    all-reduce(mean) over ranks (FO:148-149) -> the optimizer chain on that range (FO:77-90), while the main stream goes on with
-    the next stage of backward (engine.backward_stages(): VCR joint -> vision, four buckets; TVQA joint -> audio -> vision, five).
-    The buckets in ONE program order on ONE stream, the same on every rank; with the library's RCCL communicator the whole sequence
-    is capturable (FinetuneGraphStep)."""
+    """Backward from the engine's dlogits with every finished gradient BUCKET handed to a second stream (optim.BucketSchedule):
+    nan_to_num -> all-reduce(mean) over ranks (FO:148-149) -> the optimizer chain on that range (FO:77-90), while the main stream goes
+    on with the next stage of backward (engine.backward_stages(): VCR joint -> vision, four buckets; TVQA joint -> audio -> vision,
+    five).  With the library's RCCL communicator the whole sequence is capturable (FinetuneGraphStep)."""
     model = state._model
-    eng, comm, p = model.engine, model.comm, model.params_store
+    eng, comm = model.engine, model.comm
     main = torch.cuda.current_stream()
     if getattr(eng, 'comm_stream', None) is None:
         eng.comm_stream = torch.cuda.Stream(device=eng.dev)
-    cs = eng.comm_stream
     buckets, cuts = eng.gradient_buckets()
-    eng.bucket_log = []
-
-    def finish(key):
-        _, lo, hi = next(b for b in buckets if b[0] == key)
-        eng.bucket_log.append(key)
-        cs.wait_stream(main)
-        with torch.cuda.stream(cs):
-            if comm is not None:
-                ops.nan_to_num_(p.grad[lo:hi])
-                comm.allreduce_mean(p.grad[lo:hi])
-            if model.shards is not None:
-                model.shards.update(key, state.apply_shard)
-            else:
-                state.apply_range(lo, hi)
+    q = BucketSchedule(state, buckets, comm, eng.comm_stream)
+    eng.bucket_log = q.log
     stages = eng.backward_stages()
     stages[0][0]()
-    finish(stages[0][1])
+    q.finish(stages[0][1], main)
     with ops.gemm_cus(comm.world if comm is not None else 1):      # a bucket's all-reduce runs beside the next towers' GEMMs
         for stage, key, is_vision in stages[1:]:
             if is_vision:
-                stage(layer_done=lambda l: finish(('vision', l)) if l in cuts else None)
+                stage(layer_done=lambda l: q.finish(('vision', l), main) if l in cuts else None)
             else:
                 stage()
-            finish(key)
-    main.wait_stream(cs)
+            q.finish(key, main)
+    main.wait_stream(eng.comm_stream)
 
 
 def finetune_train_step(state, batch, loss_fn=None, tx_fns=None, scan_minibatch=False):
@@ -517,11 +427,7 @@ def _finetune_train_step_scanned(state, batch):
         ops.nan_to_num_(p.grad)
         comm.allreduce_mean(p.grad)
     state.prepare_step()
-    if model.shards is not None:
-        for key in model.shards.table:
-            model.shards.update(key, state.apply_shard)
-    else:
-        state.apply_range(0, p.total)
+    state.apply_all()
     state.step += 1
     info = {k: float(np.mean([l[k] for l in losses])) for k in losses[0]}
     return state, _mean_over_ranks(info, eng, comm)

@@ -155,8 +155,9 @@ def construct_train_state(opt_config, model, params=None):
         raise ValueError('call model.init_from_dummy_batch(batch) first (the reference does the same: train.py:99-100)')
     if params is not None:
         model._load({'params': params})
+    old = model.trainer.state
     model.trainer.state = _trainer.construct_train_state(opt_config, model.trainer.params)
-    model.trainer.state.f32_grads = model.trainer.f32
+    model.trainer.state.f32_grads, model.trainer.state.shards = old.f32_grads, old.shards
     return TrainState(model, model.trainer.state)
 
 

@@ -8,119 +8,42 @@ apply on that range of the flat buffers, while the main / side streams continue 
 library's RCCL communicator (dist.NativeComm) the collectives are ordinary stream-ordered launches, so the whole step,
 collectives included, is ONE hipGraph.
 """
-import os
-
 import numpy as np
 import torch
 
 from . import ops
-from .engine import PretrainEngine
+from .engine import PretrainEngine, side_stream_disabled
+from .optim import AdamStepState, BucketSchedule, lr_scale_linearwarmup_cosinedecay, vision_cut_buckets
 from .params import ParamStore
 from .planner import build_plan
 from .synthetic import make_draws
 
 
-def lr_scale_linearwarmup_cosinedecay(step, num_warmup_steps, num_train_steps, final_lr_scale=0.1):
-    """pretrain/optimization.py:117-137, evaluated in float32 like jnp on an int32 step."""
-    f = np.float32
-    step = f(step)
-    if step < num_warmup_steps:
-        return float(step / f(num_warmup_steps))
-    post = (step - f(num_warmup_steps)) / f(num_train_steps - num_warmup_steps + 1.0)
-    post = min(post, f(1.0))
-    post = f(1.0) - (f(1.0) - np.cos(f(np.pi) * post, dtype=np.float32)) / f(2.0)
-    return float(f(final_lr_scale) + f(1.0 - final_lr_scale) * post)
-
-
-class TrainState:
+class TrainState(AdamStepState):
     """Counterpart of flax TrainState for this path: step counter, parameters (fp32 master + bf16 working copy),
-    optimizer state (bf16 mu, cube-coded bf16 nu) -- all inside the ParamStore's flat buffers."""
+    optimizer state (bf16 mu, cube-coded bf16 nu) -- all inside the ParamStore's flat buffers.  The optax chain of
+    pretrain/optimization.py:180-190: no bias correction unless the config asks (optimization.py:177)."""
+    eps = 1e-8
+    bias_correction = False
 
-    def __init__(self, params, opt_config):
-        self.params = params
-        self.opt_config = dict(opt_config)
-        self.step = 0
-        self.f32_grads = False          # use_bfloat16_grads = False: the chain reads params.grad32 (set by Trainer(bf16_grads=False))
-        self.shards = None              # zero.MomentShards: mu / nu partitioned over the ranks (Trainer(shard_optimizer=True))
+    @property
+    def params(self):
+        return self.store
 
-    def _scalars(self):
-        """(sched, neg_lr, bias_corr1, bias_corr2) of the current step: scale_by_schedule uses its own count, evaluated
-        BEFORE the increment (first update is zero); no bias correction unless the config asks (optimization.py:177)."""
+    def _schedule(self):
         oc = self.opt_config
-        assert oc.get('use_bfloat16_adam', True), 'only the bf16-state Adam of the reference configs is implemented'
-        sched = lr_scale_linearwarmup_cosinedecay(self.step, oc['num_warmup_steps'], oc['num_train_steps'],
-                                                  oc.get('final_lr_scale', 0.02))
-        b1, b2 = oc.get('beta_1', 0.9), oc.get('beta_2', 0.98)
-        bc1 = bc2 = 1.0
-        if oc.get('do_bias_correction', False):
-            bc1, bc2 = 1.0 - b1 ** (self.step + 1), 1.0 - b2 ** (self.step + 1)
-        return sched, -oc['learning_rate'], bc1, bc2
+        return lr_scale_linearwarmup_cosinedecay(self.step, oc['num_warmup_steps'], oc['num_train_steps'], oc.get('final_lr_scale', 0.02))
 
-    def apply_gradients(self):
-        """optax chain of optimization.py:180-190 + apply_updates, one fused launch over the flat buffers."""
-        oc, p = self.opt_config, self.params
-        if self.shards is not None:      # partitioned moments: bucket by bucket, each rank its chunk (zero.py); a COLLECTIVE
-            self.prepare_step()
-            for key in self.shards.table:
-                self.shards.update(key, self.apply_shard)
-            self.finish_step()
-            return
-        if self.f32_grads:               # fp32 gradients: the device-scalar form of the same chain over the whole buffer
-            self.prepare_step()
-            self.apply_range(0, p.total)
-            self.finish_step()
-            return
-        sched, neg_lr, bc1, bc2 = self._scalars()
-        ops.adam_bf16_update(p.master, p.work, p.grad, p.mu, p.nu, p.decay_flags, oc.get('beta_1', 0.9), oc.get('beta_2', 0.98),
-                             oc.get('eps', 1e-8), oc['weight_decay_rate'], sched, neg_lr, bc1, bc2)
-        p.update_transposed()
-        self.step += 1
-
-    # ---- the same update in pieces: per-step scalars in a device vector (so the launches can sit inside a hipGraph) and
-    # one launch per finished range of the flat gradient buffer, overlapped with the rest of backward (trainer.Trainer)
-    def prepare_step(self):
-        """Write this step's scalars into the device vector the captured Adam launches read: a ring of two pinned host
-        vectors, each rewritten only after the copy that last read it has completed, so the host may run ahead of the stream."""
-        dev = self.params.device
-        if getattr(self, 'hyper', None) is None:
-            self.hyper = torch.zeros(4, dtype=torch.float32, device=dev)
-            self._hyper_host = [torch.zeros(4, dtype=torch.float32, pin_memory=dev.type == 'cuda') for _ in range(2)]
-            self._hyper_ev, self._hyper_turn = [None, None], 0
-        i = self._hyper_turn
-        self._hyper_turn ^= 1
-        if self._hyper_ev[i] is not None:
-            self._hyper_ev[i].synchronize()
-        sched, neg_lr, bc1, bc2 = self._scalars()
-        self._hyper_host[i].copy_(torch.tensor([sched, neg_lr, 1.0 / bc1, 1.0 / bc2], dtype=torch.float32))
-        self.hyper.copy_(self._hyper_host[i], non_blocking=True)
-        if dev.type == 'cuda':
-            self._hyper_ev[i] = torch.cuda.Event()
-            self._hyper_ev[i].record()
-
-    def apply_range(self, lo, hi, mu=None, nu=None, transposed=True):
-        """mu / nu: the moments of [lo, hi) when they do not live at p.mu[lo:hi] (zero.MomentShards)."""
-        oc, p = self.opt_config, self.params
-        assert lo % 2048 == 0 and hi % 2048 == 0
-        grad = p.grad32 if self.f32_grads else p.grad
-        ops.adam_bf16_update_dev(p.master[lo:hi], p.work[lo:hi], grad[lo:hi], p.mu[lo:hi] if mu is None else mu,
-                                 p.nu[lo:hi] if nu is None else nu, None,
-                                 p.decay_flags[lo // 2048:hi // 2048], oc.get('beta_1', 0.9), oc.get('beta_2', 0.98),
-                                 oc.get('eps', 1e-8), oc['weight_decay_rate'], self.hyper)
-        if transposed:
-            p.update_transposed(lo, hi)
-
-    def apply_shard(self, lo, hi, mu, nu):
-        self.apply_range(lo, hi, mu=mu, nu=nu, transposed=False)      # (MomentShards.update rewrites the bucket's transposed copies)
-
-    def finish_step(self):
-        self.step += 1
+    def _host_update(self, sched, neg_lr, bc1, bc2):
+        p = self.store
+        ops.adam_bf16_update(p.master, p.work, p.grad, p.mu, p.nu, p.decay_flags, *self._adam_args(), sched, neg_lr, bc1, bc2)
 
     # ---- checkpoint form: flax `to_state_dict(TrainState)` of the reference's optax chain (optimization.py:180-195):
     # opt_state = (ScaleByAdamState{count, mu, nu}, add_decayed_weights (empty), ScaleByScheduleState{count}, scale (empty))
     # serialised as dicts keyed '0'..'3' (merlot_reserve_amd/checkpoint.py writes / reads the msgpack file)
     def state_dict(self):
-        p = self.params
-        mu, nu = (p.mu, p.nu) if self.shards is None else self.shards.full_moments()      # (partitioned: a collective)
+        p = self.store
+        mu, nu = self._moments()
         return {'step': self.step, 'params': p.master_tree(),
                 'opt_state': {'0': {'count': torch.tensor(self.step, dtype=torch.int32), 'mu': p._to_tree(mu), 'nu': p._to_tree(nu)},
                               '1': {}, '2': {'count': torch.tensor(self.step, dtype=torch.int32)}, '3': {}}}
@@ -128,27 +51,12 @@ class TrainState:
     def load_state_dict(self, sd, reset_schedule=False):
         """reset_schedule = True is the resolution-adaptation restart (pretrain/train_fixres.py:94-113): parameters and the
         Adam moments are kept, the step and the schedule's count start again from 0."""
-        p = self.params
-        p.load_tree(sd['params'])
+        self.store.load_tree(sd['params'])
         self.step = int(sd.get('step', 0))
         opt = sd.get('opt_state')
         if opt:
             adam = opt['0']
-            hosts = []
-            for tree in (adam['mu'], adam['nu']):
-                host = torch.zeros(p.total, dtype=torch.bfloat16)
-                for name, fshape, *_ in p.specs:
-                    o, n = p.offsets[name]
-                    leaf = tree
-                    for k in name.split('/'):
-                        leaf = leaf[k]
-                    host[o:o + n] = leaf.reshape(-1).to(torch.bfloat16)
-                hosts.append(host)
-            if self.shards is None:
-                p.mu.copy_(hosts[0])
-                p.nu.copy_(hosts[1])
-            else:
-                self.shards.store_moments(hosts[0], hosts[1])
+            self._load_moments(adam['mu'], adam['nu'])
             self.step = int(adam.get('count', self.step))
         if reset_schedule:
             self.step = 0
@@ -160,7 +68,7 @@ def construct_train_state(opt_config, params):
 
 class Trainer:
     f32 = False          # (instances built by __init__ set it from bf16_grads)
-    shards = None        # (zero.MomentShards when built with shard_optimizer=True)
+    shards = property(lambda self: self.state.shards)      # (zero.MomentShards when built with shard_optimizer=True; the state owns them)
 
     metrics_ring = 0     # (depth of the step-metrics ring; 0 = none, the program of every caller that does not ask for it)
 
@@ -190,11 +98,10 @@ class Trainer:
         self.comm_stream = torch.cuda.Stream(device=self.device) if self.device.type == 'cuda' else None
         self.graph = None
         self._make_buckets()
-        self.shards = None
         if shard_optimizer:
             assert self.use_comm, 'shard_optimizer needs a communicator (its world may be 1)'
             from .zero import MomentShards
-            self.shards = self.state.shards = MomentShards(self.params, self.buckets, comm)
+            self.state.shards = MomentShards(self.params, self.buckets, comm)
         if self.use_comm:
             assert comm.world == world and comm.rank == rank
             R, H = self.engine.R, self.engine.d.H
@@ -206,29 +113,10 @@ class Trainer:
             self._init_metrics_ring()
 
     def _make_buckets(self):
-        """Gradient buckets = ranges of the flat buffers in the order backward makes them final (params.py lays the towers
-        out in that order, and a tower's layers in ascending order, which backward walks downwards):
-          'joint'   [scales, head, span, joint, token]        final after backward_stage_joint
-          'audio'   the audio tower                            final when the side stream's audio backward ends
-          ('vision', l)  vision layers >= l (+ final_ln, cls_proj, attention pool), down to the previous cut
-          'vision_end'   the rest of the vision tower (first layers, pre_ln, cls, patch embedding)
-        The vision tower (the last to finish) is cut at 2/3 and 1/3 of its depth, so only ~1/3 of its gradients -- < 10 % of
-        all gradient bytes for base and large -- is reduced after the last backward kernel."""
-        tr, offs, Lv = self.params.tower_ranges, self.params.offsets, self.engine.d.Lv
-        a0, a1 = tr['audio_encoder']
-        v0, v1 = tr['vision_encoder']
-        assert a1 == v0 and v1 == self.params.total
-        cuts = sorted({l for l in (Lv - Lv // 3, Lv - 2 * (Lv // 3)) if 0 < l < Lv}, reverse=True)
-        lo_of = lambda l: offs[f'vision_encoder/transformer/layer_{l:02d}/pre_attn_ln/scale'][0]
-        self.buckets = [('joint', 0, a0), ('audio', a0, a1)]
-        hi = v1
-        for l in cuts:
-            self.buckets.append((('vision', l), lo_of(l), hi))
-            hi = lo_of(l)
-        self.buckets.append(('vision_end', v0, hi))
-        self.vision_cuts = cuts
-        assert all(lo % 2048 == 0 and hi_ % 2048 == 0 and lo < hi_ for _, lo, hi_ in self.buckets)
-        assert sum(hi_ - lo for _, lo, hi_ in self.buckets) == self.params.total
+        """optim.vision_cut_buckets behind 'joint' = [scales, head, span, joint, token] (final after backward_stage_joint) and
+        'audio' = the audio tower (final when the side stream's audio backward ends)."""
+        a0, a1 = self.params.tower_ranges['audio_encoder']
+        self.buckets, self.vision_cuts = vision_cut_buckets(self.params, self.engine.d.Lv, [('joint', 0, a0), ('audio', a0, a1)])
 
     def plan(self, batch, draws=None):
         if draws is None:
@@ -247,61 +135,32 @@ class Trainer:
         else:
             eng.loss_and_grad_outputs()
 
-    def _finish_bucket(self, key, producer, update):
-        """The bucket's gradients are final on stream `producer`: on the comm stream, behind them, nan_to_num + all-reduce
-        (pretrain_model.py:328-329) and the optimizer update of that range, while the producer goes on with backward.
-        Buckets are enqueued in ONE program order on ONE stream, the same on every rank, as RCCL requires."""
-        _, lo, hi = next(b for b in self.buckets if b[0] == key)
-        self.bucket_log.append(key)
-        # (MR_NO_COMM_STREAM=1, bench.py's exclusive timing pass: the bucket's kernels are issued in line -- beside a bucket's Adam kernel a
-        # whole-CU GEMM of either tower waits for CUs, and its HIP-event duration would include that wait)
-        cs = producer if os.environ.get('MR_NO_COMM_STREAM') == '1' else self.comm_stream
-        cs.wait_stream(producer)
-        tl = getattr(self, 'bucket_timeline', None)          # (eager steps only) HIP events around the bucket's collective: bench.py --gpus N
-
-        def ev():
-            if tl is None:
-                return None
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            return e
-        with torch.cuda.stream(cs):
-            g = (self.params.grad32 if self.f32 else self.params.grad)[lo:hi]
-            e_ready = ev()
-            if self.use_comm:
-                ops.nan_to_num_(g)
-                self.comm.allreduce_mean(g)
-            e_reduced = ev()
-            if update and self.shards is not None:
-                self.shards.update(key, self.state.apply_shard)
-            elif update:
-                self.state.apply_range(lo, hi)
-            e_updated = ev()
-        if tl is not None:
-            tl.append((str(key), (hi - lo) * g.element_size() / 1e6, e_ready, e_reduced, e_updated))
-
     def _backward_reduce_update(self, update=True):
+        """Backward with every finished gradient bucket handed to the comm stream (optim.BucketSchedule).  `bucket_timeline` (eager
+        steps only: train_step_timeline) receives HIP events around each bucket's collective: bench.py --gpus N."""
         eng = self.engine
         main = torch.cuda.current_stream()
-        self.bucket_log = []
+        q = BucketSchedule(self.state, self.buckets, self.comm if self.use_comm else None, self.comm_stream, update,
+                           getattr(self, 'bucket_timeline', None))
+        self.bucket_log = q.log
         eng.backward_stage_joint()
-        self._finish_bucket('joint', main, update)
+        q.finish('joint', main)
         # from here to the end of backward a bucket's all-reduce is in flight beside the GEMMs: leave its kernel two CUs per XCD
         with ops.gemm_cus(self.world if self.use_comm else 1):
             eng.side_stream.wait_stream(main)
             eng._on_side(eng.backward_stage_audio)
-            audio_stream = main if os.environ.get('MR_NO_SIDE_STREAM') == '1' else eng.side_stream     # (A/B switch: issued in line)
+            audio_stream = main if side_stream_disabled() else eng.side_stream     # (issued in line)
             pending = ['audio']                     # enqueued behind the first vision bucket: audio rarely ends before it
 
             def layer_done(l):
                 if l in self.vision_cuts:
-                    self._finish_bucket(('vision', l), main, update)
+                    q.finish(('vision', l), main)
                     if pending:
-                        self._finish_bucket(pending.pop(), audio_stream, update)
+                        q.finish(pending.pop(), audio_stream)
             eng.backward_stage_vision(layer_done=layer_done)
             if pending:
-                self._finish_bucket(pending.pop(), audio_stream, update)
-            self._finish_bucket('vision_end', main, update)
+                q.finish(pending.pop(), audio_stream)
+            q.finish('vision_end', main)
         main.wait_stream(eng.side_stream)
         main.wait_stream(self.comm_stream)
 

@@ -85,8 +85,8 @@ class TVQAEngine(FinetuneEngine):
         self.tj = TowerState(d.n * d.Sj, H, d.Lj, d.n, d.Sj, dev)
         # static tables: "rotary" / pool rows of the two input towers (the joint tower's "rotary" table depends on the batch's segment
         # indices: it is part of the plan)
-        t = {k: torch.as_tensor(v).to(dev) for k, v in static_tables(d).items()}
-        self.vit_rot, self.vit_pool_rows, self.audio_rot, self.audio_pool_rows = t['vit_rot'], t['vit_pool_rows'], t['audio_rot'], t['audio_pool_rows']
+        t = static_tables(d)
+        self.tables = {k: torch.as_tensor(t[k]).to(dev) for k in ('vit_rot', 'vit_pool_rows', 'audio_rot', 'audio_pool_rows')}
         # static transpose of the image-row tiling: every image row is read by the 2 A sequences of its example
         ip, ix = tvqa_image_transpose(d)
         self.visT = (torch.from_numpy(ip).to(dev), torch.from_numpy(ix).to(dev))
@@ -129,15 +129,15 @@ class TVQAEngine(FinetuneEngine):
         # vision tower on the B nseg frames (F:166-168)
         self._images2d = images.reshape(d.Nv * d.hw, d.pp3)
         self.fgemm(self._images2d, 'vision_encoder/embedding/kernel', tv.xin, bias=W['vision_encoder/embedding/bias'], row_map=(d.hw, d.Sv, 1))
-        self._tower_with_pool_forward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.vit_rot,
-                                      self.vit_pool_rows, self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po, self.v_probs,
+        self._tower_with_pool_forward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.tables['vit_rot'],
+                                      self.tables['vit_pool_rows'], self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po, self.v_probs,
                                       self.imgs_seq, self.v_cls)
         # audio tower on the B nseg 3 clips (F:191-197): the stride-2 conv is a GEMM over 2 consecutive hops = 130 inputs
         ops.pad_cols(audio_clips.reshape(d.Na * d.a_len, d.a_patch * 65), self.a_in)
         self._audio2d = self.a_in[:, :d.a_patch * 65]
         self.fgemm(self._audio2d, 'audio_encoder/embedding/kernel', ta.xin, bias=W['audio_encoder/embedding/bias'], row_map=(d.a_len, d.Sa, 1))
-        self._tower_with_pool_forward(ta, 'audio_encoder/transformer', 'audio_encoder/seq_attnpool', self.audio_rot,
-                                      self.audio_pool_rows, self.a_qin, self.a_q, self.a_k, self.a_v, self.a_po, self.a_probs,
+        self._tower_with_pool_forward(ta, 'audio_encoder/transformer', 'audio_encoder/seq_attnpool', self.tables['audio_rot'],
+                                      self.tables['audio_pool_rows'], self.a_qin, self.a_q, self.a_k, self.a_v, self.a_po, self.a_probs,
                                       self.audio_seq, self.a_cls)
         # joint tower on the 2 A B sequences (F:242-246)
         ops.segment_sum([W['token_encoder/Embed_0/embedding'], self.audio_seq, self.imgs_seq], self._pl('joint_gather_indptr'),
@@ -162,17 +162,14 @@ class TVQAEngine(FinetuneEngine):
         return [(self.backward_stage_joint, 'joint', False), (self.backward_stage_audio, 'audio', False),
                 (self.backward_stage_vision, 'vision_end', True)]
 
-    def gradient_buckets(self):
-        """'joint' = [proj, joint tower, token table]; 'audio' = the audio tower; then the vision tower's cuts as in VCREngine."""
+    def head_buckets(self):
+        """'joint' = [proj, joint tower, token table]; 'audio' = the audio tower"""
         a0, a1 = self.p.tower_ranges['audio_encoder']
-        return self._buckets_with_vision_cuts([('joint', 0, a0), ('audio', a0, a1)])
+        return [('joint', 0, a0), ('audio', a0, a1)]
 
     def backward_stage_joint(self):
-        d, W, G, tj = self.d, self.W, self.p.g, self.tj
-        dl = self.dlogits[:, :1]
-        self.gemm(dl, self.pooled_h, G['proj/kernel'], transA=True)                   # d proj [1, H] = dlogits^T . pooled_h
-        self.gemm(dl, W['proj/kernel'], self.d_pooled)                                # d pooled_h = dlogits . proj^T
-        ops.segment_sum([self.d_pooled], self._pl('poolT_indptr'), self._pl('poolT_idx'), self.Dj)   # zero except the pooled rows
+        G, tj = self.G, self.tj
+        self._backward_proj_head()
         tr = self._begin_tower_reductions()
         Dj = self.encoder_backward(tj, 'joint_transformer', self._pl('joint_rot'), self._pl('joint_code'), self.Dj, tr=tr)
         self._flush_tower_reductions(tr)
@@ -182,23 +179,11 @@ class TVQAEngine(FinetuneEngine):
         ops.segment_sum([Dj], self.visT[0], self.visT[1], self.d_imgs_seq)
 
     def backward_stage_audio(self):
-        self.cur = self.sc_side
+        self.cur = self.sc_side          # (the audio tower's view of the scratch set: its own d_k / d_v, see __init__)
         try:
-            self._backward_audio()
+            super().backward_stage_audio()
         finally:
             self.cur = self.sc_main
-
-    def _backward_audio(self):
-        d, G, ta = self.d, self.p.g, self.ta
-        tr = self._begin_tower_reductions()
-        Da = self._tower_with_pool_backward(ta, 'audio_encoder/transformer', 'audio_encoder/seq_attnpool', self.audio_rot,
-                                            self.audio_pool_rows, self.a_qin, self.a_q, self.a_k, self.a_v, self.a_po,
-                                            self.a_probs, self.d_audio_seq, self.d_a_cls, self.Da, tr=tr)
-        Dp = self.cur.Dpatch[:d.Na * d.a_len]
-        ops.segment_sum([Da], self.unpad_a[0], self.unpad_a[1], Dp)
-        self._t_colsum(tr, Dp, G['audio_encoder/embedding/bias'])
-        self._flush_tower_reductions(tr)
-        self.gemm(self._audio2d, Dp, G['audio_encoder/embedding/kernel'], transA=True)
 
     def loss_info(self):
         la = self.loss_acc.tolist()

@@ -236,7 +236,7 @@ def test_training_reduces_the_contrastive_loss(dev):
     (7.34 = sum over objectives of ln(#candidates)): forward, backward and the folded optimizer work together over many
     steps.  (text_to_audio and stuff_to_span are memorised; imgs_to_audio stays at chance on iid-noise frames, whose ViT
     embeddings are nearly identical.)  The descent goes plateau by plateau (6.0 -> 5.6 -> 5.2 -> 4.6 -> 4.0 ...) and WHEN a
-    plateau is left is sensitive to single-ulp differences of bf16 gradients (scripts/step_ab.py, scripts/conv_dbg.py: five
+    plateau is left is sensitive to single-ulp differences of bf16 gradients (scripts/conv_dbg.py: five
     reduction schedules whose gradients differ by one ulp in < 10 elements are anywhere between 5.66 and 4.2 after 300 steps, and
     between 4.15 and 3.78 after 1000), so the bounds are loose at 100 steps and on the 1000-step value, which every schedule seen
     so far passes with margin."""
