@@ -200,7 +200,12 @@ int mr_poolattn_bwd(const void* q, const void* k, const void* v, int64_t ldkv, c
  * dst[i,:] = scale * sum_{j in [indptr[i], indptr[i+1])} src(indices[j]) for i < n_dst, H columns, bf16.
  * src(code): code < n0 -> src0 row code; code < n0+n1 -> src1 row code-n0; else src2 row code-n0-n1.
  * (src1/src2 may be NULL when n1 / n2 are 0).  Empty list -> zero row.  Accumulation in fp32, fixed order.
- * If accumulate != 0, dst += result (dst read as bf16).  dst_dtype MR_DT_BF16 or MR_DT_F32.
+ * If accumulate != 0, dst += result (dst read in its own type: bf16 for MR_DT_BF16, fp32 for MR_DT_F32).  dst_dtype MR_DT_BF16 or MR_DT_F32.
+ * The identity case (mr_version() >= 9): indptr == NULL && indices == NULL means dst row i (+)= scale * src0 row i -- the accumulation of a bf16
+ * buffer into an fp32 (or bf16) one, e.g. a micro-batch's parameter gradients into the step's fp32 accumulator.  It requires n0 == n_dst,
+ * src1 == src2 == NULL, ld0 >= H, ldd >= H and 16-byte aligned src0 / dst (MR_EINVAL otherwise; one list NULL and the other not is MR_EINVAL as
+ * before).  A streaming kernel: 16-byte vectors over a flat capped grid, each output element written by exactly one lane (no atomics);
+ * when ld0 == ldd == H the whole buffer is one flat range.
  */
 int mr_segment_sum(const void* src0, int64_t ld0, int64_t n0, const void* src1, int64_t ld1, int64_t n1,
                    const void* src2, int64_t ld2, int64_t n2,

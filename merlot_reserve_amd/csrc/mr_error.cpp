@@ -28,7 +28,7 @@ extern "C" const char* mr_last_error(void) { return g_err; }
 // 6: mr_attention_bwd_dense_mask (+ _workspace), options "ln_impl" / "gemm_xpx" / "gemm_xpanel"; the dynamic symbol table is the header's names only (round 6)
 // 7: the A/B-only options "gemm_v1_only" / "gemm5_stagger" / "gemm_xpx" / "gemm_xpanel" removed (mr_set_option on them: MR_EINVAL)
 // 8: mr_metrics_push (the step-metrics ring of the pretraining driver)
-extern "C" int mr_version(void) { return 8; }
+extern "C" int mr_version(void) { return 9; }
 
 // ---- option sets: one per handle + the process-wide defaults ----
 static MrOptions g_default_opts;

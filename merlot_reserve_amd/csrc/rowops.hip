@@ -56,6 +56,43 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(SegSrc src, const int3
     }
 }
 
+// The identity case of mr_segment_sum (no lists): dst row i (+)= scale * src row i, over parameter-sized buffers (the gradient accumulators of
+// the micro-batched step).  A streaming kernel, unlike the one-wave-per-row gather above: the [rows, H / 8] grid of 16-byte bf16 vectors is one
+// flat range walked grid-stride by a capped grid; a lane reads 8 bf16, and reads / writes 8 fp32 (two 16-byte vectors) or 8 bf16 of the
+// destination.  Every output element belongs to exactly one lane: no atomics, bitwise reproducible.  flat != 0: both leading dimensions equal
+// H, the whole buffer is one row of `nch` vectors (no division per vector).
+template <bool F32OUT>
+__global__ __launch_bounds__(256) void accumulate_rows_kernel(const __bf16* __restrict__ src, int64_t ld0, void* __restrict__ dst, int64_t ldd,
+                                                              int64_t total, int64_t nch, int flat, float scale, int accumulate) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = flat ? 0 : i / nch, c = i - r * nch;
+        float v[8];
+        unpack8(*reinterpret_cast<const u32x4*>(src + r * ld0 + 8 * c), v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] *= scale;
+        if (F32OUT) {
+            f32x4* d = reinterpret_cast<f32x4*>(static_cast<float*>(dst) + r * ldd + 8 * c);
+            f32x4 lo = {v[0], v[1], v[2], v[3]}, hi = {v[4], v[5], v[6], v[7]};
+            if (accumulate) {
+                const f32x4 o0 = d[0], o1 = d[1];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { lo[e] = o0[e] + lo[e]; hi[e] = o1[e] + hi[e]; }
+            }
+            d[0] = lo;
+            d[1] = hi;
+        } else {
+            u32x4* d = reinterpret_cast<u32x4*>(static_cast<__bf16*>(dst) + r * ldd + 8 * c);
+            if (accumulate) {
+                float old[8];
+                unpack8(*d, old);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] += old[e];
+            }
+            *d = pack8(v);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- mean over R rows
 __global__ __launch_bounds__(256) void rows_mean_fwd_kernel(const __bf16* __restrict__ src, int64_t lds,
                                                             const int32_t* __restrict__ rows, __bf16* __restrict__ dst,
@@ -550,6 +587,28 @@ extern "C" int mr_segment_sum(const void* src0, int64_t ld0, int64_t n0, const v
                               const void* src2, int64_t ld2, int64_t n2, const int32_t* indptr, const int32_t* indices,
                               void* dst, int64_t ldd, int32_t dst_dtype, int64_t n_dst, int64_t H, float scale,
                               int32_t accumulate, void* stream) {
+    if (src0 && dst && indptr == nullptr && indices == nullptr) {       // the identity case: dst row i (+)= scale * src0 row i
+        MR_CHECK_ARG(n0 == n_dst, "mr_segment_sum: without lists row i of src0 goes to row i of dst: n0 (%lld) must equal n_dst (%lld)",
+                     (long long)n0, (long long)n_dst);
+        MR_CHECK_ARG(src1 == nullptr && src2 == nullptr, "mr_segment_sum: without lists src1 and src2 must be NULL");
+        MR_CHECK_ARG(dst_dtype == MR_DT_F32 || dst_dtype == MR_DT_BF16, "mr_segment_sum: dst_dtype must be MR_DT_BF16 or MR_DT_F32");
+        MR_CHECK_ARG(n_dst > 0 && H > 0 && H % 8 == 0 && ld0 % 8 == 0 && ldd % 8 == 0 && ld0 >= H && ldd >= H,
+                     "mr_segment_sum: H and leading dims must be multiples of 8, leading dims >= H");
+        MR_CHECK_ARG(((uintptr_t)src0 | (uintptr_t)dst) % 16 == 0, "mr_segment_sum: src0 and dst must be 16-byte aligned");
+        const int flat = ld0 == H && ldd == H;
+        const int64_t nch = flat ? n_dst * (H / 8) : H / 8, total = n_dst * (H / 8);
+        int64_t blocks = (total + 255) / 256;
+        if (blocks > 2048) blocks = 2048;                               // 256 CUs x 8 workgroups; the rest is grid-strided
+        hipStream_t ist = static_cast<hipStream_t>(stream);
+        if (dst_dtype == MR_DT_F32)
+            hipLaunchKernelGGL(accumulate_rows_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ist, static_cast<const __bf16*>(src0), ld0, dst,
+                               ldd, total, nch, flat, scale, (int)accumulate);
+        else
+            hipLaunchKernelGGL(accumulate_rows_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ist, static_cast<const __bf16*>(src0), ld0, dst,
+                               ldd, total, nch, flat, scale, (int)accumulate);
+        MR_CHECK_LAUNCH("mr_segment_sum");
+        return MR_OK;
+    }
     MR_CHECK_ARG(src0 && indptr && indices && dst, "mr_segment_sum: null pointer");
     MR_CHECK_ARG((n1 == 0 || src1) && (n2 == 0 || src2), "mr_segment_sum: missing source table");
     MR_CHECK_ARG(n_dst > 0 && H > 0 && H % 8 == 0 && ldd % 8 == 0 && ld0 % 8 == 0 && ld1 % 8 == 0 && ld2 % 8 == 0,

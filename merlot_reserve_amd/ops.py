@@ -441,6 +441,23 @@ def segment_sum(srcs, indptr, indices, dst, scale=1.0, accumulate=False):
     return dst
 
 
+@_timed('rowops')
+def accumulate_rows(src, dst, scale=1.0, accumulate=True):
+    """dst[i, :] (+)= scale * src[i, :]: the identity case of mr_segment_sum (no lists), a streaming kernel for parameter-sized buffers.
+    src bf16, dst fp32 or bf16 (read in its own type when accumulate); 2-D row-major views of the same shape (leading dims may exceed
+    the width) or flat 1-D buffers of one length.  H % 8 == 0; both 16-byte aligned."""
+    if src.dim() == 1:
+        assert dst.dim() == 1 and src.is_contiguous() and dst.is_contiguous()
+        src, dst2 = src.view(1, -1), dst.view(1, -1)
+    else:
+        dst2 = dst
+    assert src.dtype == BF16 and dst2.dtype in (BF16, F32) and src.shape == dst2.shape, 'accumulate_rows: bf16 source, bf16 / fp32 destination of its shape'
+    n, H = dst2.shape
+    check(_lib.load().mr_segment_sum(src.data_ptr(), _ld(src), n, None, 0, 0, None, 0, 0, None, None, dst2.data_ptr(), _ld(dst2),
+                                     MR_DT_F32 if dst2.dtype == F32 else MR_DT_BF16, n, H, scale, int(accumulate), _stream()), 'mr_segment_sum')
+    return dst
+
+
 _PERIODIC = {}
 
 
@@ -526,6 +543,14 @@ def add_(a, b, y=None):
         check(_lib.load().mr_f32_axpby(a.data_ptr(), b.data_ptr(), 1.0, 1.0, a.numel(), _stream()), 'mr_f32_axpby')
         return y
     check(_lib.load().mr_add_bf16(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), _stream()), 'mr_add_bf16')
+    return y
+
+
+@_timed('rowops')
+def axpby_(y, x, a=1.0, b=1.0):
+    """y = a * x + b * y over flat fp32 buffers of one size (mr_f32_axpby)."""
+    assert _dense(y, x) and y.dtype == F32 and x.dtype == F32 and y.numel() == x.numel()
+    check(_lib.load().mr_f32_axpby(y.data_ptr(), x.data_ptr(), a, b, y.numel(), _stream()), 'mr_f32_axpby')
     return y
 
 

@@ -1,6 +1,6 @@
 """The pretraining loop: the counterpart of pretrain/train.py:55-145 on top of this package's own pieces.
 
-    python -m merlot_reserve_amd.train CONFIG.yaml -output_dir DIR [--synthetic] [--records-per-gpu B] [--max-steps N] [--gpus N] [--seed S]
+    python -m merlot_reserve_amd.train CONFIG.yaml -output_dir DIR [--synthetic] [--records-per-gpu B] [--micro-batches K] [--max-steps N] [--gpus N] [--seed S]
 
 data    records.ShardFeeder -> loader.PrefetchLoader (the config's train_fns), or --synthetic: synthetic.make_batch(seed + step) -> PrefetchLoader
 step    Trainer(metrics_ring=...): the latest checkpoint of DIR is restored if there is one (train.py:101), one eager train_step, Trainer.capture,
@@ -10,6 +10,8 @@ log     DIR/train_log.jsonl, one JSON line per step, written when the step's row
         step it has just enqueued.  ms_per_step / video_segments_per_sec are per drain interval, from device events around it.
 ckpt    checkpoint.save_checkpoint every device.iterations_per_loop steps and at the end, called on EVERY rank (sharded moments gather);
         fp32 leaves stay fp32 (keep_fp32) so that a restart is exact; --reference-format writes the reference's fp16 form instead.
+--micro-batches K > 1: microbatch.MicroBatchTrainer steps the GPU's B records as K micro-batches of B / K -- exactly K reference devices per GPU, the
+        loss over the keys of all gpus x K of them (the reference's device.batch_size: --gpus 8 --micro-batches K); the default 1 is Trainer as it is.
 --gpus N without a launcher around it starts N ranks under torch.distributed.run as a CHILD process before this process touches the GPU.
 
 With --synthetic a resumed run is bit-identical to an uninterrupted one (batch and draws are functions of (seed, step), the kernels reduce in a
@@ -30,6 +32,7 @@ def build_parser():
     ap.add_argument('-output_dir', dest='output_dir', default='', help='overrides device.output_dir of the config')
     ap.add_argument('--synthetic', action='store_true', help='batches from synthetic.make_batch(seed + step) instead of record shards')
     ap.add_argument('--records-per-gpu', type=int, default=None, help='records per GPU and step (default: device.batch_size // gpus)')
+    ap.add_argument('--micro-batches', type=int, default=1, help='step the records of a GPU as K micro-batches of records-per-gpu / K (exact large-batch loss)')
     ap.add_argument('--max-steps', type=int, default=None, help='stop at this step (default: optimizer.num_train_steps)')
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--seed', type=int, default=0)
@@ -46,8 +49,14 @@ def driver_settings(config, args):
     num_train_steps = int(opt.get('num_train_steps_override', opt['num_train_steps']))
     end = num_train_steps if args.max_steps is None else min(int(args.max_steps), num_train_steps)
     B = args.records_per_gpu if args.records_per_gpu is not None else max(int(dev.get('batch_size', args.gpus)) // args.gpus, 1)
-    return {'output_dir': out, 'ckpt_every': int(dev['iterations_per_loop']), 'log_every': int(dev.get('commit_every_nsteps', 50)),
-            'end_step': end, 'records_per_gpu': int(B)}
+    st = {'output_dir': out, 'ckpt_every': int(dev['iterations_per_loop']), 'log_every': int(dev.get('commit_every_nsteps', 50)),
+          'end_step': end, 'records_per_gpu': int(B)}
+    K = int(getattr(args, 'micro_batches', 1))
+    if K != 1:                               # (the default leaves the settings as they were)
+        from .microbatch import check_micro_batches
+        check_micro_batches(B, K)            # ValueError here: before any GPU call
+        st['micro_batches'] = K
+    return st
 
 
 def launch_command(argv, gpus, port):
@@ -220,7 +229,15 @@ def main(argv=None):
     B, out_dir, log_every = st['records_per_gpu'], st['output_dir'], st['log_every']
     config.setdefault('device', {})['batch_size'] = B * world                 # what the shard reader divides by the world size
     bf16 = bool(config['model'].get('use_bfloat16', True))
-    trainer = Trainer(config, B, dev, rank=rank, world=world, seed=args.seed, comm=comm, bf16_grads=bf16, metrics_ring=2 * log_every)
+    K = st.get('micro_batches', 1)
+    if K == 1:
+        trainer = Trainer(config, B, dev, rank=rank, world=world, seed=args.seed, comm=comm, bf16_grads=bf16, metrics_ring=2 * log_every)
+    else:
+        from .microbatch import MicroBatchTrainer
+        trainer = MicroBatchTrainer(config, B, dev, micro_batches=K, rank=rank, world=world, seed=args.seed, comm=comm, bf16_grads=bf16,
+                                    metrics_ring=2 * log_every)
+    if rank == 0:
+        print(f'training: gpus={world} records_per_gpu={B} micro_batches={K} (contrastive batch of {world * B} records as {world * K} devices)', flush=True)
     os.makedirs(out_dir, exist_ok=True)
     if checkpoint.latest_checkpoint(out_dir) is not None:                     # load if we can (train.py:101)
         checkpoint.load_checkpoint(out_dir, state=trainer.state)

@@ -135,13 +135,17 @@ class Trainer:
         else:
             eng.loss_and_grad_outputs()
 
+    def _bucket_schedule(self, update):
+        """The hand-over of this backward's finished buckets (microbatch.MicroBatchTrainer accumulates a bucket before it hands it over)."""
+        return BucketSchedule(self.state, self.buckets, self.comm if self.use_comm else None, self.comm_stream, update,
+                              getattr(self, 'bucket_timeline', None))
+
     def _backward_reduce_update(self, update=True):
         """Backward with every finished gradient bucket handed to the comm stream (optim.BucketSchedule).  `bucket_timeline` (eager
         steps only: train_step_timeline) receives HIP events around each bucket's collective: bench.py --gpus N."""
         eng = self.engine
         main = torch.cuda.current_stream()
-        q = BucketSchedule(self.state, self.buckets, self.comm if self.use_comm else None, self.comm_stream, update,
-                           getattr(self, 'bucket_timeline', None))
+        q = self._bucket_schedule(update)
         self.bucket_log = q.log
         eng.backward_stage_joint()
         q.finish('joint', main)
@@ -255,10 +259,13 @@ class Trainer:
         self.state.finish_step()
         return eng.loss_acc
 
+    def _local_loss_info(self):
+        return self.engine.loss_info()
+
     def loss_info(self, reduce=True):
         """Host dict of the last step's losses.  With a comm and reduce=True it is the mean over ranks, like the reference's
         pmean of loss_info (pretrain_model.py:336) -- a COLLECTIVE: every rank must call it."""
-        info = self.engine.loss_info()
+        info = self._local_loss_info()
         if self.use_comm and reduce and self.world > 1:
             keys = sorted(info)
             self.metrics[:len(keys)].copy_(torch.tensor([info[k] for k in keys], dtype=torch.float32))
