@@ -27,15 +27,34 @@ def side_stream_disabled():
     return os.environ.get('MR_NO_SIDE_STREAM') == '1'
 
 
-class TowerState:
-    """Saved activations of one TransformerEncoder (modeling.py:283-376) over M = nseq*S rows."""
+class _LayerRing:
+    """buffers[l % len(buffers)] for every layer l: what a forward-only TowerState keeps in place of one buffer per layer."""
 
-    def __init__(self, M, H, L, nseq, S, dev, dtype=BF16, keep_hpre=None):
+    def __init__(self, buffers):
+        self.buffers = buffers
+
+    def __getitem__(self, l):
+        return self.buffers[l % len(self.buffers)]
+
+
+class TowerState:
+    """Saved activations of one TransformerEncoder (modeling.py:283-376) over M = nseq*S rows.
+    saved=False (a forward-only program on ONE stream): nothing is kept for a backward -- every layer writes the same one layer's worth of
+    buffers (the residual stream alternates between two), and hpre does not exist."""
+
+    def __init__(self, M, H, L, nseq, S, dev, dtype=BF16, keep_hpre=None, saved=True):
         nh = H // 64
         z = lambda *s: torch.zeros(*s, dtype=dtype, device=dev)
         f = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
         self.M, self.H, self.L, self.nseq, self.S = M, H, L, nseq, S
         self.xin, self.xf = z(M, H), z(M, H)
+        self.stats = f(2 * L + 2, 2, M)       # [ln index][mean|rstd][row]; index 0 = pre_ln, 1+2l / 2+2l = layer l, last = final
+        if not saved:
+            self.X = _LayerRing([z(M, H), z(M, H)])
+            self.ln1, self.ln2, self.xmid, self.att = (_LayerRing([z(M, H)]) for _ in range(4))
+            self.qkv, self.hact, self.hpre = _LayerRing([z(M, 3 * H)]), _LayerRing([z(M, 4 * H)]), None
+            self.lse = _LayerRing([f(nseq, nh, S)])
+            return
         self.X = z(L + 1, M, H)
         self.ln1, self.ln2, self.xmid, self.att = z(L, M, H), z(L, M, H), z(L, M, H), z(L, M, H)
         self.qkv = z(L, M, 3 * H)
@@ -43,7 +62,6 @@ class TowerState:
         keep_hpre = dtype == BF16 if keep_hpre is None else keep_hpre
         self.hpre = z(L, M, 4 * H) if keep_hpre else None           # gelu'(pre-activation), only kept for backward
         self.lse = f(L, nseq, nh, S)
-        self.stats = f(2 * L + 2, 2, M)       # [ln index][mean|rstd][row]; index 0 = pre_ln, 1+2l / 2+2l = layer l, last = final
 
 
 class TowerEngine:

@@ -99,6 +99,7 @@ class FinetuneEngine(TowerEngine):
         return self.forward_device(*[batch[k] for k in self.device_keys])
 
     def backward(self):
+        assert not self.fwd_only, f'this program was built forward-only ({type(self).__name__}(..., train=True) has the backward)'
         for stage, _key, _cuts in self.backward_stages():
             stage()
 
@@ -127,15 +128,18 @@ class VCREngine(FinetuneEngine):
     def slice_example(batch, i):
         return {'image': batch['image'][i:i + 1], 'answers': np.asarray(batch['answers'])[i:i + 1], 'labels': np.asarray(batch['labels'])[i:i + 1]}
 
-    def __init__(self, config, B, params, device):
+    def __init__(self, config, B, params, device, train=True):
+        """train=False: the forward-only program (evaluation of a checkpoint: pred_step, finetune_eval.val_epoch) -- the same launch sequence up to
+        the logits with nothing kept for a backward: no gradient buffers (Dv, Dj, d_*, dlogits), no backward scratch (the GEMMs then run
+        without a split-K workspace), one layer's worth of tower activations and no gelu' copy (the fc1 GEMM's c2 = NULL)."""
         self.config, self.p, self.dev = config, params, torch.device(device)
         self.d = d = VCRDims(config, B)
-        self.dtype, self.fwd_only, self.W, self.G = BF16, False, params.w, params.g
+        self.dtype, self.fwd_only, self.W, self.G = BF16, not train, params.w, getattr(params, 'g', None)
         dev, H = self.dev, d.H
         z = lambda *s: torch.zeros(*s, dtype=BF16, device=dev)
         f = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
-        self.tv = TowerState(B * d.Sv, H, d.Lv, B, d.Sv, dev)
-        self.tj = TowerState(d.n * d.Sj, H, d.Lj, d.n, d.Sj, dev)
+        self.tv = TowerState(B * d.Sv, H, d.Lv, B, d.Sv, dev, saved=train)
+        self.tj = TowerState(d.n * d.Sj, H, d.Lj, d.n, d.Sj, dev, saved=train)
         # static tables: ViT rotary / pool rows; joint rotary (text: segment 0, token index 1..T; vision: pooled-grid (h, w),
         # segment 0 -- identical for every sequence: M:697-720 with token_segment_idx = 0, F:161)
         vit_rot = torch.from_numpy(rot_scale_table(np.concatenate([np.zeros((1, 2)), rotary_coords_2d(d.gh, d.gw)], 0))).to(dev)
@@ -147,29 +151,33 @@ class VCREngine(FinetuneEngine):
         coords[:d.T, 3] = (1.0 + np.arange(d.T)) / 1024.0
         coords[d.T:, :2] = rotary_coords_2d(h2, w2)
         self.joint_rot = torch.from_numpy(rot_scale_table(coords)).to(dev)
-        # static transpose of the image-row tiling: d_imgs_seq[b*V + i] = sum_j Dj[(b*2A + j)*Sj + T + i]
-        bb, ii, jj = np.meshgrid(np.arange(B), np.arange(d.V), np.arange(2 * d.A), indexing='ij')
-        ip, ix = csr_from_pairs((bb * d.V + ii).reshape(-1), ((bb * 2 * d.A + jj) * d.Sj + d.T + ii).reshape(-1), B * d.V)
-        self.visT = (torch.from_numpy(ip).to(dev), torch.from_numpy(ix).to(dev))
-        self.unpad_v = self._unpad_csr(B, d.Sv)
         G = B * d.V
         self.v_qin, self.v_q, self.v_po, self.imgs_seq = z(G, H), z(G, H), z(G, H), z(G, H)
         self.v_k, self.v_v = z(self.tv.M, H), z(self.tv.M, H)
         self.v_probs = f(G, d.nh, pr * pr)
         self.v_cls = z(B, H)
-        self.pooled_h, self.d_pooled = z(d.n, H), z(d.n, H)
+        self.pooled_h = z(d.n, H)
         self.logits = f(d.n, 8)                       # column 0 = the Dense(1) output
-        self.dlogits = z(d.n, 8)
         self.loss_acc = f(2)                          # [loss, is_right]
         self.labels_dev = torch.zeros(2 * B, dtype=I32, device=dev)
+        self.side_stream = None
+        self.plan_dev, self._plan_caps, self._plan_views, self.plan_frozen = None, {}, {}, False
+        self.cur = None
+        if self.fwd_only:
+            return
+        # static transpose of the image-row tiling: d_imgs_seq[b*V + i] = sum_j Dj[(b*2A + j)*Sj + T + i]
+        bb, ii, jj = np.meshgrid(np.arange(B), np.arange(d.V), np.arange(2 * d.A), indexing='ij')
+        ip, ix = csr_from_pairs((bb * d.V + ii).reshape(-1), ((bb * 2 * d.A + jj) * d.Sj + d.T + ii).reshape(-1), B * d.V)
+        self.visT = (torch.from_numpy(ip).to(dev), torch.from_numpy(ix).to(dev))
+        self.unpad_v = self._unpad_csr(B, d.Sv)
+        self.d_pooled = z(d.n, H)
+        self.dlogits = z(d.n, 8)
         self.Dv, self.Dj = z(self.tv.M, H), z(self.tj.M, H)
         self.d_imgs_seq, self.d_v_cls = z(G, H), z(B, H)
         Mmax = max(self.tv.M, self.tj.M)
         self.sc_main = self._make_scratch(Mmax, G, B * d.hw, H, d.nh)
         self.sc_side = self.sc_main                   # single-stream program: the two towers are strictly sequential
         self.cur = self.sc_main
-        self.side_stream = None
-        self.plan_dev, self._plan_caps, self._plan_views, self.plan_frozen = None, {}, {}, False
 
     def build_plan(self, batch):
         return build_vcr_plan(batch['answers'], self.d)
@@ -188,6 +196,7 @@ class VCREngine(FinetuneEngine):
 
     def loss_and_grad_logits(self):
         """train_loss_fn (F:188-195) on the device + dL/dlogits."""
+        assert not self.fwd_only, 'the forward-only program forms no loss gradient'
         d = self.d
         self.loss_acc.zero_()
         ops.softmax_xent(self.logits, d.A * 8, 8, self.labels_dev, 2 * d.B, d.A, 1.0 / (2 * d.B), self.loss_acc[0:1], self.loss_acc[1:2], self.dlogits)
@@ -214,7 +223,11 @@ class VCREngine(FinetuneEngine):
         ops.segment_sum([Dj], self.visT[0], self.visT[1], self.d_imgs_seq)
 
     def loss_info(self):
-        la = self.loss_acc.tolist()
+        return self.info_from(self.loss_acc.tolist())
+
+    @staticmethod
+    def info_from(la):
+        """The dict of loss_info() from a host copy of loss_acc (also the rows of the finetuning driver's metrics ring)."""
         return {'loss': la[0], 'is_right': la[1]}
 
 
@@ -233,12 +246,18 @@ class MerlotReserveVCR:
     engine_cls = VCREngine
     param_specs = staticmethod(vcr_param_specs)
 
-    def __init__(self, config, device='cuda:0', rank=0, world=1, comm=None, seed=0, shard_optimizer=False):
-        """shard_optimizer = True: the Adam moments are partitioned over the ranks of `comm` (FO:148-171; zero.py)."""
+    def __init__(self, config, device='cuda:0', rank=0, world=1, comm=None, seed=0, shard_optimizer=False, train=True, params_store=None):
+        """shard_optimizer = True: the Adam moments are partitioned over the ranks of `comm` (FO:148-171; zero.py).
+        train = False: the forward-only model (the engine's forward-only program over a parameter store without optimizer state and without a
+        gradient buffer): what evaluates a checkpoint's `params` alone (finetune/vcr/submit_to_leaderboard.py:117-122); no train state can be
+        built on it.  params_store: read the parameters of ANOTHER model's store instead of owning one (forward_only_view)."""
         self.config, self.device, self.rank, self.world, self.comm, self.seed = config, torch.device(device), rank, world, comm, seed
-        self.params_store, self.engine, self._last_tree = None, None, None
+        self.params_store, self.engine, self._last_tree = params_store, None, None
+        self.train, self._shared_store = bool(train), params_store is not None
         self.shard_optimizer, self._train_state = shard_optimizer, None      # (the FinetuneTrainState built on this model last)
         assert not shard_optimizer or comm is not None, 'shard_optimizer needs a communicator (its world may be 1)'
+        assert train or not shard_optimizer, 'a forward-only model has no optimizer state to shard'
+        assert params_store is None or not train, 'only a forward-only model may read another model\'s parameter store'
 
     @property
     def shards(self):
@@ -251,12 +270,20 @@ class MerlotReserveVCR:
             raise ValueError("config must have 'model' and 'data' sections (the reference's YAML schema)")
         return cls(config, **kwargs)
 
+    def forward_only_view(self):
+        """A forward-only model of the same class that READS THIS MODEL'S working parameters (no copy: a step of this model is seen by the
+        next forward of the view): the driver's validation pass.  Its engine is built for the batch size of its first batch."""
+        assert self.params_store is not None, 'call init_from_dummy_batch(batch) first'
+        return type(self)(self.config, device=self.device, seed=self.seed, train=False, params_store=self.params_store)
+
     def _ensure(self, batch):
         B = self.engine_cls.batch_size(batch)
         if self.engine is None:
-            self.params_store = ParamStore(self.config, self.device, seed=self.seed, specs=self.param_specs(self.config),
-                                           decay_rule=decay_finetune, with_orig=True, with_optimizer=not self.shard_optimizer)
-            self.engine = self.engine_cls(self.config, B, self.params_store, self.device)
+            if self.params_store is None:
+                self.params_store = ParamStore(self.config, self.device, seed=self.seed, specs=self.param_specs(self.config),
+                                               decay_rule=decay_finetune, with_orig=self.train,
+                                               with_optimizer=self.train and not self.shard_optimizer, with_grad=self.train)
+            self.engine = self.engine_cls(self.config, B, self.params_store, self.device, train=self.train)
         elif self.engine.d.B != B:
             raise ValueError(f'this model was initialised for {self.engine.d.B} examples per device, got {B}')
         return self.engine
@@ -269,6 +296,7 @@ class MerlotReserveVCR:
     def _load(self, variables):
         if variables is None:
             return
+        assert not self._shared_store, 'this forward-only view reads another model\'s parameters: load them there'
         tree = variables['params'] if 'params' in variables else variables
         if tree is not self._last_tree:
             # a pretrained tree still holds audio_encoder / head / span_encoder (popped at F:181-183) -- they are not read
@@ -343,6 +371,8 @@ def construct_finetuning_train_state(opt_config, model, params=None, only_state=
     """FO:56-105.  Returns (state, tx_fns) like the reference (tx_fns is None: the chain is one fused kernel)."""
     if model.engine is None:
         raise ValueError('call model.init_from_dummy_batch(batch) first')
+    if not model.train:
+        raise ValueError('a forward-only model (train=False) has no optimizer state: build the model with train=True')
     if params is not None:
         model._load({'params': params})
     state = FinetuneTrainState(model, opt_config)
@@ -356,6 +386,17 @@ def train_loss_fn(state, params, batch):
     model.engine.loss_and_grad_logits()
     info = model.engine.loss_info()
     return info['loss'], info
+
+
+def _model_of(state_or_model):
+    """pred_step takes a train state (as the reference's does) or a model, forward-only ones included."""
+    return getattr(state_or_model, '_model', state_or_model)
+
+
+def pred_step(state_or_model, batch):
+    """F:202-204: {'logprobs': log_softmax(logits) [B, 2, A], 'preds': argmax [B, 2]}; host arithmetic on the 2 B A logits."""
+    logits = _model_of(state_or_model).apply(None, batch).float().cpu()
+    return {'logprobs': torch.log_softmax(logits, -1), 'preds': torch.argmax(logits, -1)}
 
 
 def _backward_reduce_update(state):

@@ -40,10 +40,12 @@ def _stage(dst, src):
 
 
 class PrefetchLoader:
-    def __init__(self, batches, device, depth=2, dtype=torch.bfloat16):
-        """batches: an iterable of host batches (numpy arrays or CPU tensors for FLOAT_KEYS; anything else is passed through).
-        depth >= 2: slots in the pinned and device rings (1 batch being consumed + depth - 1 in flight)."""
+    def __init__(self, batches, device, depth=2, dtype=torch.bfloat16, keys=FLOAT_KEYS):
+        """batches: an iterable of host batches (numpy arrays or CPU tensors for `keys`; anything else is passed through).
+        depth >= 2: slots in the pinned and device rings (1 batch being consumed + depth - 1 in flight).
+        keys: the float arrays this loader moves (the pretraining batch's by default; a VCR batch has 'image')."""
         assert depth >= 2
+        self.keys = tuple(keys)
         self.it = iter(batches)
         self.device = torch.device(device)
         self.depth, self.dtype = depth, dtype
@@ -59,8 +61,8 @@ class PrefetchLoader:
             self._issue()
 
     def _alloc(self, slot, batch):
-        self.pinned[slot] = {k: torch.empty(tuple(batch[k].shape), dtype=self.dtype, pin_memory=self.cuda) for k in FLOAT_KEYS}
-        self.dev[slot] = {k: torch.empty(tuple(batch[k].shape), dtype=self.dtype, device=self.device) for k in FLOAT_KEYS}
+        self.pinned[slot] = {k: torch.empty(tuple(batch[k].shape), dtype=self.dtype, pin_memory=self.cuda) for k in self.keys}
+        self.dev[slot] = {k: torch.empty(tuple(batch[k].shape), dtype=self.dtype, device=self.device) for k in self.keys}
 
     def _issue(self):
         """Take the next host batch and start its transfer into the next slot.  Returns False at the end of the data."""
@@ -70,11 +72,11 @@ class PrefetchLoader:
             return False
         slot = self.turn
         self.turn = (self.turn + 1) % self.depth
-        if self.pinned[slot] is None or any(tuple(batch[k].shape) != tuple(self.pinned[slot][k].shape) for k in FLOAT_KEYS):
+        if self.pinned[slot] is None or any(tuple(batch[k].shape) != tuple(self.pinned[slot][k].shape) for k in self.keys):
             self._alloc(slot, batch)
         if self.h2d_done[slot] is not None:
             self.h2d_done[slot].synchronize()                     # the pinned slot's previous copy has left it
-        for k in FLOAT_KEYS:
+        for k in self.keys:
             src = batch[k]
             src = torch.from_numpy(np.ascontiguousarray(src)) if isinstance(src, np.ndarray) else src
             _stage(self.pinned[slot][k], src)                     # host-side cast to the wire dtype + memcpy into pinned memory
@@ -82,15 +84,15 @@ class PrefetchLoader:
             with torch.cuda.stream(self.copy_stream):
                 if self.consumed[slot] is not None:
                     self.copy_stream.wait_event(self.consumed[slot])   # the step that read this device slot has finished
-                for k in FLOAT_KEYS:
+                for k in self.keys:
                     self.dev[slot][k].copy_(self.pinned[slot][k], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.copy_stream)
             self.h2d_done[slot] = ev
         else:
-            for k in FLOAT_KEYS:
+            for k in self.keys:
                 self.dev[slot][k].copy_(self.pinned[slot][k])
-        self.queue.append((slot, {k: v for k, v in batch.items() if k not in FLOAT_KEYS}))
+        self.queue.append((slot, {k: v for k, v in batch.items() if k not in self.keys}))
         return True
 
     def release(self):

@@ -152,7 +152,8 @@ def decay_finetune(flax_shape):
 
 class ParamStore:
     def __init__(self, config, device, seed=0, with_optimizer=True, init=True, specs=None, decay_rule=decay_pretrain,
-                 with_orig=False):
+                 with_orig=False, with_grad=True):
+        """with_grad=False (a store that only a forward-only program reads): no gradient buffer, and no `g` views."""
         self.config = config
         self.device = torch.device(device)
         self.H = config['model']['hidden_size']
@@ -173,7 +174,7 @@ class ParamStore:
         self.total = off
         self.master = torch.zeros(off, dtype=torch.float32, device=self.device)
         self.work = torch.zeros(off, dtype=torch.bfloat16, device=self.device)
-        self.grad = torch.zeros(off, dtype=torch.bfloat16, device=self.device)
+        self.grad = torch.zeros(off, dtype=torch.bfloat16, device=self.device) if with_grad else None
         if with_optimizer:
             self.mu = torch.zeros(off, dtype=torch.bfloat16, device=self.device)
             self.nu = torch.zeros(off, dtype=torch.bfloat16, device=self.device)
@@ -185,7 +186,8 @@ class ParamStore:
             o, n = self.offsets[name]
             self.w[name] = self.work[o:o + n].view(*vshape)
             self.wm[name] = self.master[o:o + n].view(*vshape)
-            self.g[name] = self.grad[o:o + n].view(*vshape)
+            if with_grad:
+                self.g[name] = self.grad[o:o + n].view(*vshape)
         # Transposed bf16 working copies of the Dense kernels ([in, out] -> [out, in]): what the FORWARD GEMMs read, so that
         # both of a GEMM's operands are contraction-contiguous (the dgrads get that from the flax layout as it is).  Same
         # offsets as `work`; rewritten after every change of `work` (update_transposed: one HBM-bound pass, 4 B / parameter).

@@ -28,7 +28,7 @@ import torch
 
 from . import ops
 from .engine import BF16, F32, I32, TowerState
-from .finetune import FinetuneEngine, FinetuneGraphStep, MerlotReserveVCR
+from .finetune import FinetuneEngine, FinetuneGraphStep, MerlotReserveVCR, _model_of
 from .params import VOCAB, tvqa_param_specs
 from .planner import AUDIOSPAN, MASK, build_tvqa_plan, static_tables, tvqa_image_transpose
 
@@ -73,24 +73,21 @@ class TVQAEngine(FinetuneEngine):
                 'textonly_seqs': np.asarray(batch['textonly_seqs'])[i:i + 1], 'audio_seqs': np.asarray(batch['audio_seqs'])[i:i + 1],
                 'labels': np.asarray(batch['labels'])[i:i + 1]}
 
-    def __init__(self, config, B, params, device):
+    def __init__(self, config, B, params, device, train=True):
+        """train=False: the forward-only program, as finetune.VCREngine's."""
         self.config, self.p, self.dev = config, params, torch.device(device)
         self.d = d = TVQADims(config, B)
-        self.dtype, self.fwd_only, self.W, self.G = BF16, False, params.w, params.g
+        self.dtype, self.fwd_only, self.W, self.G = BF16, not train, params.w, getattr(params, 'g', None)
         dev, H = self.dev, d.H
         z = lambda *s: torch.zeros(*s, dtype=BF16, device=dev)
         f = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
-        self.tv = TowerState(d.Nv * d.Sv, H, d.Lv, d.Nv, d.Sv, dev)
-        self.ta = TowerState(d.Na * d.Sa, H, d.La, d.Na, d.Sa, dev)
-        self.tj = TowerState(d.n * d.Sj, H, d.Lj, d.n, d.Sj, dev)
+        self.tv = TowerState(d.Nv * d.Sv, H, d.Lv, d.Nv, d.Sv, dev, saved=train)
+        self.ta = TowerState(d.Na * d.Sa, H, d.La, d.Na, d.Sa, dev, saved=train)
+        self.tj = TowerState(d.n * d.Sj, H, d.Lj, d.n, d.Sj, dev, saved=train)
         # static tables: "rotary" / pool rows of the two input towers (the joint tower's "rotary" table depends on the batch's segment
         # indices: it is part of the plan)
         t = static_tables(d)
         self.tables = {k: torch.as_tensor(t[k]).to(dev) for k in ('vit_rot', 'vit_pool_rows', 'audio_rot', 'audio_pool_rows')}
-        # static transpose of the image-row tiling: every image row is read by the 2 A sequences of its example
-        ip, ix = tvqa_image_transpose(d)
-        self.visT = (torch.from_numpy(ip).to(dev), torch.from_numpy(ix).to(dev))
-        self.unpad_v, self.unpad_a = self._unpad_csr(d.Nv, d.Sv), self._unpad_csr(d.Na, d.Sa)
         Gv, Ga = d.Nv * d.V, d.Na * d.a_tok
         self.v_qin, self.v_q, self.v_po, self.imgs_seq = z(Gv, H), z(Gv, H), z(Gv, H), z(Gv, H)
         self.v_k, self.v_v = z(self.tv.M, H), z(self.tv.M, H)
@@ -102,11 +99,21 @@ class TVQAEngine(FinetuneEngine):
         self.a_k, self.a_v = z(self.ta.M, H), z(self.ta.M, H)
         self.a_probs = f(Ga, d.nh, d.a_pool)
         self.a_cls = z(d.Na, H)
-        self.pooled_h, self.d_pooled = z(d.n, H), z(d.n, H)
+        self.pooled_h = z(d.n, H)
         self.logits = f(d.n, 8)                       # column 0 = the Dense(1) output; rows [0, A B) audio stream, [A B, 2 A B) text stream
-        self.dlogits = z(d.n, 8)
         self.loss_acc = f(4)                          # [loss_audio, is_right_audio, loss_text, is_right_text]
         self.labels_dev = torch.zeros(B, dtype=I32, device=dev)
+        self.side_stream = None
+        self.plan_dev, self._plan_caps, self._plan_views, self.plan_frozen = None, {}, {}, False
+        self.cur = None
+        if self.fwd_only:
+            return
+        # static transpose of the image-row tiling: every image row is read by the 2 A sequences of its example
+        ip, ix = tvqa_image_transpose(d)
+        self.visT = (torch.from_numpy(ip).to(dev), torch.from_numpy(ix).to(dev))
+        self.unpad_v, self.unpad_a = self._unpad_csr(d.Nv, d.Sv), self._unpad_csr(d.Na, d.Sa)
+        self.d_pooled = z(d.n, H)
+        self.dlogits = z(d.n, 8)
         self.Dv, self.Da, self.Dj = z(self.tv.M, H), z(self.ta.M, H), z(self.tj.M, H)
         self.d_imgs_seq, self.d_audio_seq = z(Gv, H), z(Ga, H)
         self.d_v_cls, self.d_a_cls = z(d.Nv, H), z(d.Na, H)           # the cls outputs feed nothing: their gradients stay zero
@@ -118,8 +125,6 @@ class TVQAEngine(FinetuneEngine):
         self.sc_side = copy.copy(self.sc_main)
         self.sc_side.d_k, self.sc_side.d_v = z(self.ta.M, H), z(self.ta.M, H)
         self.cur = self.sc_main
-        self.side_stream = None
-        self.plan_dev, self._plan_caps, self._plan_views, self.plan_frozen = None, {}, {}, False
 
     def build_plan(self, batch):
         return build_tvqa_plan(batch['textonly_seqs'], batch['audio_seqs'], self.d)
@@ -150,6 +155,7 @@ class TVQAEngine(FinetuneEngine):
 
     def loss_and_grad_logits(self):
         """train_loss_fn (F:277-294) on the device + dL/dlogits: one A-way cross-entropy per stream, each the mean over B."""
+        assert not self.fwd_only, 'the forward-only program forms no loss gradient'
         d = self.d
         AB = d.A * d.B
         self.loss_acc.zero_()
@@ -186,7 +192,11 @@ class TVQAEngine(FinetuneEngine):
             self.cur = self.sc_main
 
     def loss_info(self):
-        la = self.loss_acc.tolist()
+        return self.info_from(self.loss_acc.tolist())
+
+    @staticmethod
+    def info_from(la):
+        """The dict of loss_info() from a host copy of loss_acc (also the rows of the finetuning driver's metrics ring)."""
         return {'loss': la[0] + la[2], 'is_right_audio': la[1], 'is_right_text': la[3], 'loss_audio': la[0], 'loss_text': la[2]}
 
 
@@ -200,6 +210,7 @@ class MerlotReserveTVQA(MerlotReserveVCR):
     def _load(self, variables):
         if variables is None:
             return
+        assert not self._shared_store, 'this forward-only view reads another model\'s parameters: load them there'
         tree = variables['params'] if 'params' in variables else variables
         if tree is not self._last_tree:
             # a pretrained tree still holds head / span_encoder (popped at F:269-270) and contrastive_scales -- they are not read --
@@ -218,9 +229,9 @@ def train_loss_fn(state, params, batch):
     return info.pop('loss'), info
 
 
-def pred_step(state, batch):
-    """F:300-310: host arithmetic on the 2 B A logits."""
-    la, lt = state._model.apply(None, batch)
+def pred_step(state_or_model, batch):
+    """F:300-310: host arithmetic on the 2 B A logits.  Takes a train state, or a model (a forward-only one included)."""
+    la, lt = _model_of(state_or_model).apply(None, batch)
     la, lt = la.float().cpu(), lt.float().cpu()
     out = {'logprobs_audio': torch.log_softmax(la, -1), 'preds_audio': torch.argmax(la, -1),
            'logprobs_text': torch.log_softmax(lt, -1), 'preds_text': torch.argmax(lt, -1)}
