@@ -29,7 +29,7 @@ import json
 import os
 import sys
 
-from .train import checkpoint_due
+from .driver import IntervalTimer, JsonlLog, checkpoint_due, epoch_due, init_rank, new_event, self_launch, truncate_log
 
 TASKS = {'vcr': dict(num_answers=4, lang_seq_len=144, train_size=212736), 'tvqa': dict(num_answers=5, lang_seq_len=256, train_size=122112, num_segments=7)}
 RESTART_PREFIX = 'restart_'
@@ -103,28 +103,6 @@ def driver_settings(config, args):
             'records_per_gpu': dev['batch_size'] // gpus, 'val_batch_size': int(args.val_batch_size or dev['batch_size'])}
 
 
-def launch_command(argv, gpus, port):
-    """The child command of `--gpus N` without a launcher: N fresh ranks of this module under torch.distributed.run."""
-    return [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={gpus}', '--master-addr', '127.0.0.1',
-            '--master-port', str(port), '-m', 'merlot_reserve_amd.finetune_train'] + list(argv)
-
-
-def _self_launch(argv, gpus):
-    import socket
-    import subprocess
-    with socket.socket() as sk:
-        sk.bind(('127.0.0.1', 0))
-        port = sk.getsockname()[1]
-    env = dict(os.environ)
-    env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-    return subprocess.run(launch_command(argv, gpus, port), env=env).returncode
-
-
-def epoch_due(step, epoch_every):
-    """After `step` steps in all: the end of an epoch (V:259) -- checkpoint, restart file, validation."""
-    return step > 0 and step % epoch_every == 0
-
-
 class LaggedLog:
     """The lagged log of V:250-257: pushed(n) -- step n has been enqueued -- writes the row of step n - log_every, which has long left the
     device; flush(n_done) writes what is left at the end of the run.  read(step) returns the step's row (waiting, if at all, for that step only);
@@ -142,51 +120,6 @@ class LaggedLog:
         while self.next < n_done:
             self.write(self.read(self.next))
             self.next += 1
-
-
-class IntervalMs:
-    """ms per step of each log interval from device events recorded at its two ends.  of(step) answers for the LAST step of an interval
-    only (one figure per interval) and waits for the interval's closing event, which lies directly behind that step's metrics copy.
-    Work that is no step (an epoch's checkpoint and validation pass) is kept out: mark(step) before it closes the running interval,
-    resume(step) after it opens the next one with a fresh event."""
-
-    def __init__(self, start_step, new_event, examples_per_step):
-        self.new_event, self.examples = new_event, examples_per_step
-        self.intervals = []                                # (first step, steps done at its end, opening event, closing event)
-        self.open = (start_step, new_event())
-
-    def mark(self, step):
-        lo, e0 = self.open
-        if step > lo:
-            e1 = self.new_event()
-            self.intervals.append((lo, step, e0, e1))
-            self.open = (step, e1)
-
-    def resume(self, step):
-        self.mark(step)
-        self.open = (step, self.new_event())
-
-    def of(self, step):
-        for lo, hi, e0, e1 in self.intervals:
-            if hi == step + 1:
-                e1.synchronize()
-                ms = e0.elapsed_time(e1) / (hi - lo)
-                return {'ms_per_step': ms, 'examples_per_sec': self.examples / (ms / 1e3) if ms > 0 else None}
-        return {}
-
-
-def truncate_log(path, keep):
-    """A resumed run starts at its restart file's step, which may lie before the last row an interrupted run wrote: drop the rows (JSON lines)
-    for which keep(row) is false, so that no step or epoch is logged twice.  Returns the number of rows dropped."""
-    if not os.path.exists(path):
-        return 0
-    lines = [line for line in open(path) if line.strip()]
-    kept = [line for line in lines if keep(json.loads(line))]
-    if len(kept) != len(lines):
-        with open(path + '.tmp', 'w') as f:
-            f.writelines(kept)
-        os.replace(path + '.tmp', path)
-    return len(lines) - len(kept)
 
 
 class MetricsRing:
@@ -276,7 +209,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = build_parser().parse_args(argv)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        return _self_launch(argv, args.gpus)
+        return self_launch('merlot_reserve_amd.finetune_train', argv, args.gpus)
 
     import torch
     from . import checkpoint
@@ -289,16 +222,7 @@ def main(argv=None):
     task = args.task
     config = task_overrides(load_config(args.pretrain_config_file), task, args)
     st = driver_settings(config, args)
-    world, rank, local_rank = (int(os.environ.get(k, d)) for k, d in (('WORLD_SIZE', '1'), ('RANK', '0'), ('LOCAL_RANK', '0')))
-    assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}'
-    torch.cuda.set_device(local_rank)
-    dev = torch.device('cuda', local_rank)
-    comm = None
-    if world > 1:
-        import torch.distributed as dist
-        from .dist import NativeComm
-        dist.init_process_group('gloo', rank=rank, world_size=world)          # control plane only: rendezvous + the RCCL id
-        comm = NativeComm.from_torch_distributed(dev)
+    dev, comm, rank, world = init_rank(args.gpus)
     B, out_dir, log_every = st['records_per_gpu'], st['output_dir'], st['log_every']
     os.makedirs(out_dir, exist_ok=True)
     if args.synthetic_shards:
@@ -330,19 +254,9 @@ def main(argv=None):
     if rank == 0:                                                             # rows an interrupted run wrote past its last restart file are run again
         truncate_log(os.path.join(out_dir, 'train_log.jsonl'), lambda row: row['step'] < start)
         truncate_log(os.path.join(out_dir, 'val_log.jsonl'), lambda row: row['step'] <= start)
-    log = open(os.path.join(out_dir, 'train_log.jsonl'), 'a') if rank == 0 else None
-
-    def new_event():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
-    timer = IntervalMs(start, new_event, world * B)
-
-    def write(row):
-        if log is not None:
-            log.write(json.dumps(dict(row, **timer.of(row['step']))) + '\n')
-            log.flush()
-    lagged = LaggedLog(log_every, ring.row, write, first_step=start)
+    log = JsonlLog(os.path.join(out_dir, 'train_log.jsonl'), rank)
+    timer = IntervalTimer(start, new_event, world * B, 'examples_per_sec', last_row_only=True)
+    lagged = LaggedLog(log_every, ring.row, lambda row: log.write(dict(row, **timer.of(row['step']))), first_step=start)
 
     def end_of_epoch(step):
         if rank != 0:
@@ -396,8 +310,7 @@ def main(argv=None):
         lagged.flush(step)
     finally:
         reader.close()
-        if log is not None:
-            log.close()
+        log.close()
     if rank == 0:
         print(f'ran {step - start} steps to step {state.step}; log, checkpoints and predictions in {out_dir}', flush=True)
     if comm is not None:

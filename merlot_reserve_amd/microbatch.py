@@ -26,12 +26,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .engine import PretrainEngine
 from .optim import BucketSchedule
-from .params import ParamStore
 from .planner import build_plan
 from .synthetic import make_draws
-from .trainer import Trainer, construct_train_state
+from .trainer import Trainer
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
@@ -77,30 +75,13 @@ class MicroBatchTrainer(Trainer):
                  metrics_ring=0):
         if not bf16_grads or shard_optimizer:
             raise ValueError('MicroBatchTrainer: the fp32-gradient program (bf16_grads=False) and sharded moments (shard_optimizer=True) are out of scope')
-        K = int(micro_batches)
-        b = check_micro_batches(B, K)
-        self.config, self.B, self.K, self.b, self.rank, self.world = config, B, K, b, rank, world
-        self.device = torch.device(device)
-        self.f32 = False
-        self.params = ParamStore(config, self.device, seed=seed)
-        self.params.enable_f32_grads()
-        self.state = construct_train_state(config['optimizer'], self.params)
-        self.state.f32_grads = True          # the bucket chain reads the fp32 accumulator; the engine keeps writing the bf16 params.grad
+        self.K = int(micro_batches)
+        self.b = check_micro_batches(B, self.K)
         # ONE engine of b records; it is virtual device rank * K + m among world * K when micro-batch m's loss is issued
-        self.engine = PretrainEngine(config, b, self.params, self.device, rank=0, world=world * K, train=True)
-        self.comm = comm
-        assert world == 1 or comm is not None
-        self.use_comm = comm is not None
-        self.comm_stream = torch.cuda.Stream(device=self.device) if self.device.type == 'cuda' else None
-        self.graph = None
-        self._make_buckets()
-        if self.use_comm:
-            assert comm.world == world and comm.rank == rank
-            self.metrics = torch.zeros(8, dtype=F32, device=self.device)
-        self._make_step_buffers()
-        self.metrics_ring = int(metrics_ring)
-        if self.metrics_ring:
-            self._init_metrics_ring()
+        super().__init__(config, B, device, rank=rank, world=world, seed=seed, comm=comm, metrics_ring=metrics_ring,
+                         engine_shape=(self.b, 0, world * self.K))
+        self.params.enable_f32_grads()
+        self.state.f32_grads = True          # the bucket chain reads the fp32 accumulator; the engine keeps writing the bf16 params.grad
 
     def _make_step_buffers(self):
         eng, K, W, dev = self.engine, self.K, self.world, self.device
@@ -201,7 +182,7 @@ class MicroBatchTrainer(Trainer):
     def _push_metrics(self):
         if self.metrics_ring:                # before phase C: the scales are the ones this step's forwards read
             ops.metrics_push(self.loss_sum, self.diag_sum, self.params.wm['contrastive_scales'], self.state.hyper,
-                             self._m_ring, self._m_steps, self._m_counter)
+                             *self.step_metrics.tensors)
 
     # ---- steps ----
     def train_step(self, batch, plan=None, draws=None, update=True):
@@ -211,7 +192,8 @@ class MicroBatchTrainer(Trainer):
         plans = self.plan(batch, draws) if plan is None else plan
         assert len(plans) == K
         self.state.prepare_step()
-        self._metrics_begin_step()
+        if self.metrics_ring:
+            self.step_metrics.begin_step(self.state.step)
         for m in range(K):
             eng.set_plan(plans[m])
             eng.forward_device(*self._inputs(batch, m))
@@ -266,7 +248,8 @@ class MicroBatchTrainer(Trainer):
         gA, gC, gLast = self.graph
         assert len(plan) == K
         self.state.prepare_step()
-        self._metrics_begin_step()
+        if self.metrics_ring:
+            self.step_metrics.begin_step(self.state.step)
         for m in range(K):
             eng.set_plan(plan[m])
             self._stage_inputs(batch, m)

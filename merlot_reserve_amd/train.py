@@ -17,10 +17,11 @@ ckpt    checkpoint.save_checkpoint every device.iterations_per_loop steps and at
 With --synthetic a resumed run is bit-identical to an uninterrupted one (batch and draws are functions of (seed, step), the kernels reduce in a
 fixed order, the Adam scalars are functions of the step).  With shards the reader starts again from its seed, as the reference's does."""
 import argparse
-import json
 import math
 import os
 import sys
+
+from .driver import IntervalTimer, JsonlLog, checkpoint_due, init_rank, new_event, self_launch
 
 OBJECTIVES = ('imgs_to_audio', 'text_to_audio', 'stuff_to_span')      # order of contrastive_scales (pretrain/train.py:134-139)
 TIMING_KEYS = ('ms_per_step', 'video_segments_per_sec')
@@ -59,28 +60,6 @@ def driver_settings(config, args):
     return st
 
 
-def launch_command(argv, gpus, port):
-    """The child command of `--gpus N` without a launcher: N fresh ranks of this module under torch.distributed.run."""
-    return [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={gpus}', '--master-addr', '127.0.0.1',
-            '--master-port', str(port), '-m', 'merlot_reserve_amd.train'] + list(argv)
-
-
-def _self_launch(argv, gpus):
-    import socket
-    import subprocess
-    with socket.socket() as sk:
-        sk.bind(('127.0.0.1', 0))
-        port = sk.getsockname()[1]
-    env = dict(os.environ)
-    env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-    return subprocess.run(launch_command(argv, gpus, port), env=env).returncode
-
-
-def checkpoint_due(step, ckpt_every, end_step):
-    """After `step` steps in all: every ckpt_every steps of the RUN'S step count (a resumed run keeps the cadence) and at the end."""
-    return step % ckpt_every == 0 or step == end_step
-
-
 def log_record(row, timing=None):
     """One line of train_log.jsonl from a row of Trainer.drain_metrics."""
     rec = {k: v for k, v in row.items() if k != 'contrastive_scales'}
@@ -89,29 +68,6 @@ def log_record(row, timing=None):
         rec[f'temperature/{name}/exp'] = math.exp(v)
     rec.update(timing or {})
     return rec
-
-
-class IntervalTimer:
-    """ms per step of each drain interval from device events recorded at the drains; an interval's events are read when its rows have come
-    back (they are behind the copy that brought the rows), so reading them does not wait either."""
-
-    def __init__(self, start_step, new_event, segments_per_step):
-        self.new_event, self.segments = new_event, segments_per_step
-        self.marks = [(start_step, new_event())]           # (steps done, event recorded behind them)
-        self.done = {}
-
-    def mark(self, step):
-        if step > self.marks[-1][0]:
-            self.marks.append((step, self.new_event()))
-
-    def of(self, step):
-        for (lo, e0), (hi, e1) in zip(self.marks, self.marks[1:]):
-            if lo <= step < hi:
-                if hi not in self.done:
-                    ms = e0.elapsed_time(e1) / (hi - lo)
-                    self.done[hi] = {'ms_per_step': ms, 'video_segments_per_sec': self.segments / (ms / 1e3) if ms > 0 else None}
-                return self.done[hi]
-        return {}
 
 
 def run_loop(trainer, feed, *, end_step, log_every, ckpt_every, save, write, timer=None, use_graph=True):
@@ -204,7 +160,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = build_parser().parse_args(argv)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        return _self_launch(argv, args.gpus)
+        return self_launch('merlot_reserve_amd.train', argv, args.gpus)
 
     import torch
     from . import checkpoint, records
@@ -215,16 +171,7 @@ def main(argv=None):
     config = load_config(args.config_file)
     config['_path'] = args.config_file
     st = driver_settings(config, args)
-    world, rank, local_rank = (int(os.environ.get(k, d)) for k, d in (('WORLD_SIZE', '1'), ('RANK', '0'), ('LOCAL_RANK', '0')))
-    assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}'
-    torch.cuda.set_device(local_rank)
-    dev = torch.device('cuda', local_rank)
-    comm = None
-    if world > 1:
-        import torch.distributed as dist
-        from .dist import NativeComm
-        dist.init_process_group('gloo', rank=rank, world_size=world)          # control plane only: rendezvous + the RCCL id
-        comm = NativeComm.from_torch_distributed(dev)
+    dev, comm, rank, world = init_rank(args.gpus)
 
     B, out_dir, log_every = st['records_per_gpu'], st['output_dir'], st['log_every']
     config.setdefault('device', {})['batch_size'] = B * world                 # what the shard reader divides by the world size
@@ -253,32 +200,22 @@ def main(argv=None):
         source = feeder = records.ShardFeeder(config, rank=rank, world=world, seed=args.seed, workers=workers)
     feed = PrefetchLoader(source, dev, depth=2, dtype=torch.bfloat16)
 
-    log = open(os.path.join(out_dir, 'train_log.jsonl'), 'a') if rank == 0 else None
-
-    def write(row, timing):
-        if log is not None:
-            log.write(json.dumps(log_record(row, timing)) + '\n')
-            log.flush()
+    log = JsonlLog(os.path.join(out_dir, 'train_log.jsonl'), rank)
 
     def save(step):
         fn = checkpoint.save_checkpoint(trainer.state, out_dir, rank=rank, keep_fp32=not args.reference_format)
         if rank == 0:
             print(f'saved {fn}', flush=True)
 
-    def new_event():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
-
-    timer = IntervalTimer(start, new_event, world * B * config['data']['num_segments'])
+    timer = IntervalTimer(start, new_event, world * B * config['data']['num_segments'], 'video_segments_per_sec')
     use_graph = bf16 and (comm is None or comm.capturable)
     try:
-        n = run_loop(trainer, feed, end_step=st['end_step'], log_every=log_every, ckpt_every=st['ckpt_every'], save=save, write=write,
+        n = run_loop(trainer, feed, end_step=st['end_step'], log_every=log_every, ckpt_every=st['ckpt_every'], save=save,
+                     write=lambda row, timing: log.write(log_record(row, timing)),
                      timer=timer, use_graph=use_graph)
     finally:
         feeder.close()
-        if log is not None:
-            log.close()
+        log.close()
     torch.cuda.synchronize()
     if rank == 0:
         print(f'ran {n} steps to step {trainer.state.step}; log and checkpoints in {out_dir}', flush=True)

@@ -13,6 +13,7 @@ import torch
 
 from . import ops
 from .engine import PretrainEngine, side_stream_disabled
+from .metrics import StepMetricsRing
 from .optim import AdamStepState, BucketSchedule, lr_scale_linearwarmup_cosinedecay, vision_cut_buckets
 from .params import ParamStore
 from .planner import build_plan
@@ -71,8 +72,10 @@ class Trainer:
     shards = property(lambda self: self.state.shards)      # (zero.MomentShards when built with shard_optimizer=True; the state owns them)
 
     metrics_ring = 0     # (depth of the step-metrics ring; 0 = none, the program of every caller that does not ask for it)
+    step_metrics = None  # (metrics.StepMetricsRing of that depth)
 
-    def __init__(self, config, B, device, rank=0, world=1, seed=0, comm=None, bf16_grads=True, shard_optimizer=False, metrics_ring=0):
+    def __init__(self, config, B, device, rank=0, world=1, seed=0, comm=None, bf16_grads=True, shard_optimizer=False, metrics_ring=0,
+                 engine_shape=None):
         """bf16_grads = False is the reference's use_bfloat16_grads = False step (pretrain/pretrain_model.py:323-333; train.py:61-67): the
         fp32 master parameters are differentiated, the gradients stay fp32 through nan_to_num / pmean and enter the Adam chain as
         fp32 -- the fp32 program of the engine (mr_f32_* kernels, eager, several times slower than the bf16 step: the correctness
@@ -81,14 +84,16 @@ class Trainer:
         shard_optimizer = True: the Adam moments are partitioned over the ranks of `comm` (pretrain/train_fixres.py:178-199; zero.py).
         metrics_ring = depth > 0: every step pushes its raw loss accumulators, temperatures and schedule scalar into a device ring of `depth`
         rows (one mr_metrics_push launch inside the step, captured with it); drain_metrics() reads them back without stalling the stream --
-        the lagged log of pretrain/train.py:119-129.  0 allocates nothing and leaves the launch sequence as it is."""
+        the lagged log of pretrain/train.py:119-129.  0 allocates nothing and leaves the launch sequence as it is.
+        engine_shape = (records, rank, world) of the engine where they are not (B, rank, world): microbatch.MicroBatchTrainer."""
         self.config, self.B, self.rank, self.world = config, B, rank, world
         self.device = torch.device(device)
         self.f32 = not bf16_grads
         self.params = ParamStore(config, self.device, seed=seed, with_optimizer=not shard_optimizer)          # same seed on every rank: replicated init
         self.state = construct_train_state(config['optimizer'], self.params)
         self.state.f32_grads = self.f32
-        self.engine = PretrainEngine(config, B, self.params, self.device, rank=rank, world=world,
+        eB, erank, eworld = engine_shape or (B, rank, world)
+        self.engine = PretrainEngine(config, eB, self.params, self.device, rank=erank, world=eworld,
                                      dtype=torch.float32 if self.f32 else torch.bfloat16, train=True)
         self.comm = comm
         # the collective path runs whenever a comm is given -- also with a single rank, which is how the RCCL calls
@@ -104,13 +109,17 @@ class Trainer:
             self.state.shards = MomentShards(self.params, self.buckets, comm)
         if self.use_comm:
             assert comm.world == world and comm.rank == rank
-            R, H = self.engine.R, self.engine.d.H
-            z = lambda *s: torch.zeros(*s, dtype=self.engine.dtype, device=self.device)
-            self.E_all, self.dE_all, self.dE_red = z(world, R, H), z(world, R, H), z(R, H)
             self.metrics = torch.zeros(8, dtype=torch.float32, device=self.device)
+        self._make_step_buffers()
         self.metrics_ring = int(metrics_ring)
         if self.metrics_ring:
-            self._init_metrics_ring()
+            self.step_metrics = StepMetricsRing(self.metrics_ring, self.device, self.engine.info_from, len(self.engine.objectives) + 4, comm)
+
+    def _make_step_buffers(self):
+        if self.use_comm:
+            R, H = self.engine.R, self.engine.d.H
+            z = lambda *s: torch.zeros(*s, dtype=self.engine.dtype, device=self.device)
+            self.E_all, self.dE_all, self.dE_red = z(self.world, R, H), z(self.world, R, H), z(R, H)
 
     def _make_buckets(self):
         """optim.vision_cut_buckets behind 'joint' = [scales, head, span, joint, token] (final after backward_stage_joint) and
@@ -173,7 +182,7 @@ class Trainer:
         self._loss_and_exchange()
         if self.metrics_ring:            # before backward: the scales are the ones this step's forward read, not the updated ones
             ops.metrics_push(self.engine.loss_acc, self.engine.diag, self.params.wm['contrastive_scales'], self.state.hyper,
-                             self._m_ring, self._m_steps, self._m_counter)
+                             *self.step_metrics.tensors)
         self._backward_reduce_update(update=True)
 
     # ---- pieces, for tests and for the reference-API adapter (eager) ----
@@ -198,7 +207,8 @@ class Trainer:
             plan = self.plan(batch, draws)
         self.state.prepare_step()
         eng.set_plan(plan)
-        self._metrics_begin_step()
+        if self.metrics_ring:
+            self.step_metrics.begin_step(self.state.step)
         self._program(batch['images'], batch['audio_clips'])
         self.state.finish_step()
         return eng.loss_acc
@@ -254,7 +264,8 @@ class Trainer:
         self.images_in.copy_(batch['images'], non_blocking=True)
         self.audio_in.copy_(batch['audio_clips'], non_blocking=True)
         eng.set_plan(plan)
-        self._metrics_begin_step()
+        if self.metrics_ring:
+            self.step_metrics.begin_step(self.state.step)
         self.graph.replay()
         self.state.finish_step()
         return eng.loss_acc
@@ -273,126 +284,7 @@ class Trainer:
             info = dict(zip(keys, self.metrics[:len(keys)].tolist()))
         return info
 
-    # ---- step-metrics ring: the log of a step that is one replayed graph, read without a synchronise per step ----
-    def _init_metrics_ring(self):
-        depth, L = self.metrics_ring, ops.METRICS_ROW
-        assert depth >= 2, 'metrics_ring: a depth of at least 2 (twice a drain interval of one step)'
-        cuda = self.device.type == 'cuda'
-        # ONE buffer [depth rows of L floats | depth int32 step numbers], so a drain is one D2H copy
-        self._m_buf = torch.zeros(depth * (L + 1), dtype=torch.float32, device=self.device)
-        self._m_ring = self._m_buf[:depth * L].view(depth, L)
-        self._m_steps = self._m_buf[depth * L:].view(torch.int32)
-        self._m_steps.copy_(torch.full((depth,), -1, dtype=torch.int32))          # no row holds a step yet
-        self._m_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._m_host = [torch.zeros(depth * (L + 1), dtype=torch.float32, pin_memory=cuda) for _ in range(2)]
-        self._m_turn = 0
-        self._m_copy_stream = torch.cuda.Stream(device=self.device) if cuda else None
-        self._m_first = None              # step of the first push (set with the device counter, at the first step)
-        self._m_pushed = self._m_drained = 0          # steps [drained, pushed) are in the ring and not yet copied
-        self._m_raw = None                # (lo, hi, event, pinned buffer): a ring copy in flight
-        self._m_red = None                # (rows, keys, event, pinned buffer): an average over ranks in flight
-        nk = len(self.engine.objectives) + 4
-        self._m_red_dev = torch.zeros((depth // 2) * nk, dtype=torch.float32, device=self.device) if self.use_comm else None
-        self._m_red_host = torch.zeros((depth // 2) * nk, dtype=torch.float32, pin_memory=cuda) if self.use_comm else None      # (read back before its next use)
-
-    def _metrics_begin_step(self):
-        if not self.metrics_ring:
-            return
-        if self._m_first is None:         # once: the device counter starts at the step this trainer starts from (0, or a restored step)
-            self._m_first = self._m_pushed = self._m_drained = self.state.step
-            self._m_counter.copy_(torch.tensor([self.state.step], dtype=torch.int32))
-        assert self._m_pushed == self.state.step, 'the metrics ring counts the steps of train_step / train_step_graph'
-        self._m_pushed += 1
-
-    @staticmethod
-    def metrics_rows(host, depth, lo, hi, derive):
-        """Rows of the steps [lo, hi) out of a host copy of the ring buffer ([depth, METRICS_ROW] floats, then depth int32 step numbers).
-        The step number stored with a row must be the expected one: a lost or overwritten row raises, it is never returned as data."""
-        L = ops.METRICS_ROW
-        vals = host[:depth * L].view(depth, L).tolist()
-        steps = host[depth * L:].view(torch.int32).tolist()
-        rows = []
-        for step in range(lo, hi):
-            r = step % depth
-            if steps[r] != step:
-                raise RuntimeError(f'metrics ring: row {r} holds step {steps[r]}, expected {step} (overwritten or never written)')
-            v = vals[r]
-            row = {'step': step}
-            row.update(derive(v[0:3], [v[3:9], v[9:15]]))
-            row['contrastive_scales'], row['lr_scale'] = v[15:18], v[18]
-            rows.append(row)
-        return rows
-
-    def _metrics_enqueue_copy(self):
-        lo, hi = self._m_drained, self._m_pushed
-        host = self._m_host[self._m_turn]
-        self._m_turn ^= 1
-        if self.device.type != 'cuda':
-            host.copy_(self._m_buf)
-            self._m_raw = (lo, hi, None, host)
-        else:
-            main = torch.cuda.current_stream()
-            ready = torch.cuda.Event()
-            ready.record(main)                                   # the pushes of [lo, hi) are on the main stream before this point
-            with torch.cuda.stream(self._m_copy_stream):
-                self._m_copy_stream.wait_event(ready)
-                host.copy_(self._m_buf, non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(self._m_copy_stream)
-            main.wait_event(done)                                # device-side: no later step writes a row while this copy reads the ring
-            self._m_raw = (lo, hi, done, host)
-        self._m_drained = hi
-
-    def _metrics_enqueue_mean(self, rows):
-        """The derived rows averaged over the ranks: ONE allreduce_mean_f32 behind the steps already enqueued, and a copy back
-        (pretrain_model.py:336, once per drain instead of once per step) -- a COLLECTIVE."""
-        keys = sorted(k for k in rows[0] if k not in ('step', 'contrastive_scales', 'lr_scale'))
-        n = len(rows) * len(keys)
-        host = self._m_red_host
-        host[:n].copy_(torch.tensor([[r[k] for k in keys] for r in rows], dtype=torch.float32).view(-1))
-        dev = self._m_red_dev[:n]
-        dev.copy_(host[:n], non_blocking=True)
-        self.comm.allreduce_mean_f32(dev)
-        host[:n].copy_(dev, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._m_red = (rows, keys, ev, host)
-
-    def _metrics_collect(self):
-        """Whatever has arrived on the host: the averaged rows in flight, then the raw copy in flight (derived; with a comm, sent on to be averaged)."""
-        out = []
-        if self._m_red is not None:
-            rows, keys, ev, host = self._m_red
-            ev.synchronize()
-            vals = host[:len(rows) * len(keys)].view(len(rows), len(keys)).tolist()
-            for r, v in zip(rows, vals):
-                r.update(zip(keys, v))
-            out += rows
-            self._m_red = None
-        if self._m_raw is not None:
-            lo, hi, ev, host = self._m_raw
-            if ev is not None:
-                ev.synchronize()
-            rows = self.metrics_rows(host, self.metrics_ring, lo, hi, self.engine.info_from)
-            self._m_raw = None
-            if self.use_comm and rows:
-                self._metrics_enqueue_mean(rows)
-            else:
-                out += rows
-        return out
-
     def drain_metrics(self, flush=False):
-        """Start an asynchronous copy of the ring (copy stream, behind the steps enqueued so far) and return the rows of the PREVIOUS drain as
-        [{'step', **loss_info() keys, 'contrastive_scales', 'lr_scale'}]: the host waits for a copy enqueued one drain interval ago, never for
-        the steps it has just enqueued.  With a comm the loss_info keys are means over the ranks (they arrive one drain later still) and equal
-        loss_info(reduce=True) of that step -- a COLLECTIVE: every rank drains at the same steps.  At most depth // 2 steps between two drains.
-        flush=True (end of a run): synchronises and returns everything that is left."""
+        """The rows of the step-metrics ring, one drain late (metrics.StepMetricsRing.drain) -- with a comm a COLLECTIVE."""
         assert self.metrics_ring, 'Trainer(metrics_ring=depth) was not asked for'
-        n = self._m_pushed - self._m_drained
-        assert 2 * n <= self.metrics_ring, f'metrics ring of {self.metrics_ring} rows: at most {self.metrics_ring // 2} steps between drains, got {n}'
-        out = self._metrics_collect()
-        if n:
-            self._metrics_enqueue_copy()
-        while flush and (self._m_raw is not None or self._m_red is not None):
-            out += self._metrics_collect()
-        return out
+        return self.step_metrics.drain(flush=flush)

@@ -1,4 +1,4 @@
-"""The finetuning driver (merlot_reserve_amd/finetune_train.py), the validation arithmetic and the prediction files (finetune_eval.py) on the host:
+"""The finetuning driver (merlot_reserve_amd/finetune_train.py, driver.py), the validation arithmetic and the prediction files (finetune_eval.py) on the host:
 the per-task config overrides, the step counts, the epoch / restart cadence, the lagged log, the `--gpus N` child command, accuracies with 'pad'
 skipping, and the VCR CSV / TVQA JSON writers against hand-written text.  Nothing here touches a GPU."""
 import json
@@ -11,6 +11,7 @@ import pytest
 import torch
 import yaml
 
+from merlot_reserve_amd import driver
 from merlot_reserve_amd import finetune_eval as E
 from merlot_reserve_amd import finetune_train as FT
 from merlot_reserve_amd.config import load_config, tiny_config
@@ -127,7 +128,7 @@ def test_interval_ms_reports_once_per_interval_and_skips_epoch_work():
 
         def elapsed_time(self, other):
             return other.t - self.t
-    t = FT.IntervalMs(10, Ev, examples_per_step=4)
+    t = driver.IntervalTimer(10, Ev, 4, 'examples_per_sec', last_row_only=True)
     Ev.clock[0] = 60.0
     t.mark(12)
     t.mark(12)                                                       # no empty interval
@@ -176,7 +177,7 @@ def test_gpus_builds_a_child_launch_and_touches_no_gpu(tmp_path, monkeypatch):
     assert int(cmd[cmd.index('--master-port') + 1]) > 0
     assert not torch.cuda.is_initialized()                           # the parent has not touched the GPU
     assert not (tmp_path / 'out').exists() and not (tmp_path / 'shards').exists()      # ... nor started the run itself
-    assert FT.launch_command(['a'], 8, 1234)[3:8] == ['--nnodes=1', '--nproc-per-node=8', '--master-addr', '127.0.0.1', '--master-port']
+    assert driver.launch_command('merlot_reserve_amd.finetune_train', ['a'], 8, 1234)[3:8] == ['--nnodes=1', '--nproc-per-node=8', '--master-addr', '127.0.0.1', '--master-port']
 
 
 # ---------------------------------------------------------------------------------------------------- validation arithmetic

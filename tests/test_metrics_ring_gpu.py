@@ -127,7 +127,7 @@ def test_default_trainer_has_no_ring(dev):
     from merlot_reserve_amd.trainer import Trainer
     cfg = tiny_config(seq_len=80, lang_seq_len=40)
     tr = Trainer(cfg, 2, dev, seed=0)
-    assert tr.metrics_ring == 0 and not hasattr(tr, '_m_ring')
+    assert tr.metrics_ring == 0 and tr.step_metrics is None
     calls = []
     real = ops.metrics_push
     ops.metrics_push = lambda *a, **k: calls.append(1) or real(*a, **k)

@@ -1,7 +1,6 @@
-"""The pretraining driver (merlot_reserve_amd/train.py) and the trainer's metrics-ring bookkeeping, on the host: argument parsing and the YAML
+"""The pretraining driver (merlot_reserve_amd/train.py, driver.py) and the step-metrics ring's bookkeeping (metrics.py), on the host: argument parsing and the YAML
 keys, rows returned one drain late, a wrong stored step raises, the checkpoint cadence and the resume arithmetic with a fake trainer, the
 `--gpus N` child command.  Nothing here touches a GPU."""
-import functools
 import json
 import types
 
@@ -9,9 +8,10 @@ import pytest
 import torch
 import yaml
 
-from merlot_reserve_amd import ops, train
+from merlot_reserve_amd import driver, train
 from merlot_reserve_amd.config import tiny_config
 from merlot_reserve_amd.engine import PretrainEngine
+from merlot_reserve_amd.metrics import StepMetricsRing
 from merlot_reserve_amd.trainer import Trainer
 
 OBJECTIVES = [('imgs_to_audio',), ('text_to_audio',), ('stuff_to_span',)]
@@ -47,14 +47,11 @@ def test_arguments_and_yaml_keys(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------- the metrics ring, host side
-def _bare_trainer(depth, step=0):
-    """A Trainer's metrics-ring state on the CPU, without model or library: what drain_metrics works on."""
-    t = Trainer.__new__(Trainer)
-    t.device, t.metrics_ring, t.use_comm = torch.device('cpu'), depth, False
+def _ring(depth, step=0):
+    """A metrics ring on the CPU, without model or library, and the step count of the trainer it would belong to."""
     eng = types.SimpleNamespace(objectives=OBJECTIVES)
-    eng.info_from = functools.partial(PretrainEngine.info_from, eng)
-    t.engine, t.state = eng, types.SimpleNamespace(step=step)
-    t._init_metrics_ring()
+    t = StepMetricsRing(depth, 'cpu', lambda la, dg: PretrainEngine.info_from(eng, la, dg), len(OBJECTIVES) + 4)
+    t.state = types.SimpleNamespace(step=step)
     return t
 
 
@@ -66,13 +63,13 @@ def _sources(step):
 
 def _fake_step(t):
     """What one train_step does to the ring: the host count, and mr_metrics_push's effect written by hand."""
-    t._metrics_begin_step()
-    depth, L = t.metrics_ring, ops.METRICS_ROW
-    c = int(t._m_counter)
+    t.begin_step(t.state.step)
+    ring, steps, counter = t.tensors
+    c = int(counter)
     la, dg, sc, lr = _sources(c)
-    t._m_ring[c % depth] = torch.tensor(la + dg[0] + dg[1] + sc + [lr])
-    t._m_steps[c % depth] = c
-    t._m_counter += 1
+    ring[c % t.depth] = torch.tensor(la + dg[0] + dg[1] + sc + [lr])
+    steps[c % t.depth] = c
+    counter += 1
     t.state.step += 1
 
 
@@ -86,46 +83,46 @@ def _expected(step):
 
 @pytest.mark.parametrize('start', [0, 37])
 def test_rows_come_back_one_drain_late(start):
-    t = _bare_trainer(depth=8, step=start)
+    t = _ring(depth=8, step=start)
     for _ in range(4):
         _fake_step(t)
-    assert t.drain_metrics() == []                                   # the first drain only starts a copy
+    assert t.drain() == []                                           # the first drain only starts a copy
     for _ in range(3):
         _fake_step(t)
-    rows = t.drain_metrics()
+    rows = t.drain()
     assert rows == [_expected(start + i) for i in range(4)]          # the rows of the PREVIOUS drain, derived like loss_info()
     assert set(rows[0]) == {'step', 'imgs_to_audio', 'text_to_audio', 'stuff_to_span', 'loss', '_stuff_to_span_from_text2audio',
                             '_stuff_to_span_from_audio2text', '_stuff_to_span_from_random_text', 'contrastive_scales', 'lr_scale'}
     for _ in range(4):                                               # rows wrap: steps start + 7 ... start + 10 reuse the slots of the first four
         _fake_step(t)
-    assert [r['step'] for r in t.drain_metrics()] == [start + 4, start + 5, start + 6]
-    assert t.drain_metrics(flush=True) == [_expected(start + i) for i in range(7, 11)]
-    assert t.drain_metrics(flush=True) == [] and int(t._m_counter) == start + 11
+    assert [r['step'] for r in t.drain()] == [start + 4, start + 5, start + 6]
+    assert t.drain(flush=True) == [_expected(start + i) for i in range(7, 11)]
+    assert t.drain(flush=True) == [] and int(t.tensors[2]) == start + 11
 
 
 def test_wrong_stored_step_raises():
-    t = _bare_trainer(depth=8)
+    t = _ring(depth=8)
     for _ in range(4):
         _fake_step(t)
-    t._m_steps[2] = 10                                               # as if a later step had overwritten row 2
-    t.drain_metrics()
+    t.tensors[1][2] = 10                                             # as if a later step had overwritten row 2
+    t.drain()
     with pytest.raises(RuntimeError, match='row 2 holds step 10, expected 2'):
-        t.drain_metrics()
-    t = _bare_trainer(depth=8)
-    t._metrics_begin_step()                                          # a step whose push never ran: the row holds no step
+        t.drain()
+    t = _ring(depth=8)
+    t.begin_step(0)                                                  # a step whose push never ran: the row holds no step
     t.state.step += 1
     with pytest.raises(RuntimeError, match='expected 0'):
-        t.drain_metrics(flush=True)
+        t.drain(flush=True)
 
 
 def test_depth_must_be_twice_the_drain_interval():
-    t = _bare_trainer(depth=8)
+    t = _ring(depth=8)
     for _ in range(5):
         _fake_step(t)
     with pytest.raises(AssertionError, match='at most 4 steps between drains'):
-        t.drain_metrics()
+        t.drain()
     with pytest.raises(AssertionError):
-        _bare_trainer(depth=1)
+        _ring(depth=1)
     fake = types.SimpleNamespace(metrics_ring=6, state=types.SimpleNamespace(step=0))
     with pytest.raises(AssertionError, match='2 x the log interval'):
         train.run_loop(fake, iter(()), end_step=4, log_every=4, ckpt_every=2, save=None, write=None)
@@ -135,10 +132,10 @@ def test_depth_must_be_twice_the_drain_interval():
 
 # ---------------------------------------------------------------------------------------------------- the loop with a fake trainer
 class FakeTrainer:
-    """Counts what the loop asks for; its ring is the bare trainer's."""
+    """Counts what the loop asks for; its ring is a real one."""
 
     def __init__(self, depth, step=0):
-        self.ring = _bare_trainer(depth, step)
+        self.ring = _ring(depth, step)
         self.state, self.metrics_ring = self.ring.state, depth
         self.calls = []
 
@@ -160,7 +157,7 @@ class FakeTrainer:
 
     def drain_metrics(self, flush=False):
         self.calls.append(('flush' if flush else 'drain', self.state.step, None))
-        return self.ring.drain_metrics(flush=flush)
+        return self.ring.drain(flush=flush)
 
 
 def _batches(first):
@@ -225,7 +222,7 @@ def test_gpus_builds_a_child_launch_and_touches_no_gpu(tmp_path, monkeypatch):
     assert int(cmd[cmd.index('--master-port') + 1]) > 0
     assert not torch.cuda.is_initialized()                           # the parent has not touched the GPU (and never execs)
     assert not (tmp_path / 'out').exists()                           # ... nor started the run itself
-    assert train.launch_command(['a'], 8, 1234)[3:8] == ['--nnodes=1', '--nproc-per-node=8', '--master-addr', '127.0.0.1', '--master-port']
+    assert driver.launch_command('merlot_reserve_amd.train', ['a'], 8, 1234)[3:8] == ['--nnodes=1', '--nproc-per-node=8', '--master-addr', '127.0.0.1', '--master-port']
 
 
 def test_interval_timer_divides_an_interval_by_its_steps():
@@ -235,9 +232,12 @@ def test_interval_timer_divides_an_interval_by_its_steps():
         def __init__(self):
             self.t = Ev.clock[0]
 
+        def synchronize(self):
+            pass
+
         def elapsed_time(self, other):
             return other.t - self.t
-    t = train.IntervalTimer(100, Ev, segments_per_step=64)
+    t = driver.IntervalTimer(100, Ev, 64, 'video_segments_per_sec')
     Ev.clock[0] = 150.0
     t.mark(105)
     t.mark(105)                                                      # the end of the run marks again: no empty interval
