@@ -1,5 +1,5 @@
-"""Builds libmreserve_hip.so (gfx950) in-tree with hipcc.  No torch extension machinery: the library is a plain
-C-ABI shared object (include/mreserve_hip.h) loaded through ctypes."""
+"""Builds libmreserve_hip.so and libmreserve_media.so (gfx950) in-tree with hipcc.  No torch extension machinery: the libraries are plain
+C-ABI shared objects (include/mreserve_hip.h, include/mreserve_media.h) loaded through ctypes."""
 import os
 import subprocess
 import sys
@@ -20,7 +20,8 @@ LIB = os.path.join(HERE, 'libmreserve_hip.so')
 # in lanes 48-63 while waves of an MFMA kernel (the small 128 x 128 GEMM) share the SIMD.  f32path.hip / f32bwd.hip (not performance paths) are built
 # scalar as well; the bf16 GEMM files keep their packed epilogues (3.2 ms of the step) and are held to bit-stability under that neighbour by the test.
 EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'layernorm.hip': ['-fno-slp-vectorize'], 'rowops.hip': ['-fno-slp-vectorize'],
-               'adam.hip': ['-fno-slp-vectorize', '-ffp-contract=off'], 'f32bwd.hip': ['-fno-slp-vectorize'], 'f32path.hip': ['-fno-slp-vectorize']}
+               'adam.hip': ['-fno-slp-vectorize', '-ffp-contract=off'], 'f32bwd.hip': ['-fno-slp-vectorize'], 'f32path.hip': ['-fno-slp-vectorize'],
+               'media.hip': ['-fno-slp-vectorize']}
 # The hazard at instruction level (scripts/micro/pk_probe.hip, scripts/pk_probe.py): v_pk_add_f32 / v_pk_fma_f32 (any packed fp32 arithmetic) with an
 # `op_sel:[..1..]` source -- the LOW result element reading the HIGH register of a source pair -- returns wrong values in lanes 48-63 of a wave
 # while another kernel's MFMA waves are resident on its SIMD (0 mismatches alone; op_sel_hi, neg_lo / neg_hi, v_pk_mov_b32 op_sel are unaffected).
@@ -31,6 +32,11 @@ SLP_FILES = ['gemm.hip', 'gemm256.hip', 'gemm3.hip', 'gemm4.hip', 'gemm5.hip']  
 HAZARD_RE = r'^\s*v_pk_(add|mul|fma|min|max)_f32\b.*\bop_sel:\['
 SOURCES = ['gemm.hip', 'gemm256.hip', 'gemm3.hip', 'gemm4.hip', 'gemm5.hip', 'gemm_route.cpp', 'attention.hip', 'layernorm.hip', 'rowops.hip', 'adam.hip', 'f32path.hip', 'f32bwd.hip', 'mr_error.cpp', 'comm.cpp', 'hostio.cpp']
 HIP_FILES = [f for f in SOURCES if f.endswith('.hip')]
+# libmreserve_media.so (include/mreserve_media.h, symbols mrm_*): the media front end, a library of its own -- it needs none of the other library's
+# handles or options.  fp32 code, built scalar like the other fp32 files, scanned like them, and with no spill allowance.
+MEDIA_LIB = os.path.join(HERE, 'libmreserve_media.so')
+MEDIA_SOURCES = ['media.hip']
+MEDIA_HIP_FILES = [f for f in MEDIA_SOURCES if f.endswith('.hip')]
 # Register spills (metadata .vgpr_spill_count / .sgpr_spill_count of every kernel in the device assembly): a spill inside a k-loop costs more than any
 # schedule gains (gemm4<256,0> with 183 spilled registers: 299 vs 91 us), so build() FAILS on a kernel with spilled vector registers unless it is
 # listed here with the number it is known to carry and the reason it is tolerated.  {regex on the demangled-ish symbol: (max spilled VGPRs, why)}
@@ -64,20 +70,20 @@ def _asm_path(src):
 
 
 def _needs_build():
-    if not os.path.exists(LIB):
+    if not os.path.exists(LIB) or not os.path.exists(MEDIA_LIB):
         return True
     if not os.path.exists(STAMP):
         # a library that travelled without its build/ directory (the GPU box's snapshot carries both; a bare copy does not): trust the mtimes
         pass
     elif open(STAMP).read() != _flag_stamp():
         return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, '..', 'include', 'mreserve_hip.h')]
+    t = min(os.path.getmtime(LIB), os.path.getmtime(MEDIA_LIB))
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, '..', 'include', h) for h in ('mreserve_hip.h', 'mreserve_media.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def _asm_stale():
-    return any(not os.path.exists(_asm_path(f)) or os.path.getmtime(_asm_path(f)) < os.path.getmtime(os.path.join(CSRC, f)) for f in HIP_FILES)
+    return any(not os.path.exists(_asm_path(f)) or os.path.getmtime(_asm_path(f)) < os.path.getmtime(os.path.join(CSRC, f)) for f in HIP_FILES + MEDIA_HIP_FILES)
 
 
 def scan_packed_op_sel(files=None):
@@ -175,18 +181,19 @@ def build(force=False, verbose=True):
     if not force and not _needs_build():
         return LIB
     import json
+    all_hip = HIP_FILES + MEDIA_HIP_FILES
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     bdir = os.path.join(HERE, 'build')
     os.makedirs(bdir, exist_ok=True)
-    objs, queue, running, failed = [], [], [], []
-    for src in SOURCES:
+    objs, media_objs, queue, running, failed = [], [], [], [], []
+    for src in SOURCES + MEDIA_SOURCES:
         stem = src.rsplit('.', 1)[0]
         obj = os.path.join(bdir, stem + '.o')
         cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17'] + EXTRA_FLAGS.get(src, []) + ['-x', 'hip', '-c', os.path.join(CSRC, src), '-o', obj]
         if src.endswith('.hip'):
             cmd.append('--save-temps=obj')          # leaves <stem>-hip-amdgcn-amd-amdhsa-gfx950.s: the device assembly OF THIS OBJECT, for the scans
         queue.append((src, cmd))
-        objs.append(obj)
+        (media_objs if src in MEDIA_SOURCES else objs).append(obj)
     while queue or running:
         while queue and len(running) < JOBS:
             src, cmd = queue.pop(0)
@@ -197,19 +204,19 @@ def build(force=False, verbose=True):
             failed.append(f'hipcc failed on {src}:\n{out.decode()}')
     if failed:
         raise RuntimeError('\n'.join(failed))
-    for src in HIP_FILES:
+    for src in all_hip:
         stem = src.rsplit('.', 1)[0]
         os.replace(os.path.join(bdir, stem + '-hip-amdgcn-amd-amdhsa-gfx950.s'), _asm_path(src))
         for f in os.listdir(bdir):                  # the other intermediates (preprocessed sources, bitcode, host assembly) are not needed
             if f.startswith(stem + '-h') or f.startswith(stem + '.hip-hip-'):
                 os.remove(os.path.join(bdir, f))
-    bad = scan_packed_op_sel()
+    bad = scan_packed_op_sel(files=all_hip)
     if bad:
         raise RuntimeError('packed fp32 instructions with an op_sel source (wrong in lanes 48-63 beside MFMA waves, see build.py) in:\n' +
                            '\n'.join(f'{f}: {n} e.g. {ex}' for f, n, ex in bad) + '\nrestructure the code (SLP files: or compile with -fno-slp-vectorize)')
     with open(os.path.join(bdir, 'resources.json'), 'w') as f:
-        json.dump(kernel_resources(), f, indent=1, sort_keys=True)
-    spills = scan_spills()
+        json.dump(kernel_resources(all_hip), f, indent=1, sort_keys=True)
+    spills = scan_spills(files=all_hip)
     if spills:
         raise RuntimeError('kernels with spilled vector registers (build.py SPILL_ALLOWED lists the tolerated ones):\n' +
                            '\n'.join(f'{f}: {k}: {n} VGPRs' for f, k, n in spills))
@@ -218,10 +225,12 @@ def build(force=False, verbose=True):
     # translation units share, kernel handles and device stubs stay local (tests/test_cabi_exports.py reads `nm -D`)
     cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-z,defs', '-Wl,--version-script=' + os.path.join(CSRC, 'exports.map'), '-o', LIB] + objs + ['-ldl']
     subprocess.check_call(cmd)
+    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-z,defs', '-Wl,--version-script=' + os.path.join(CSRC, 'media_exports.map'), '-o', MEDIA_LIB] + media_objs
+    subprocess.check_call(cmd)
     with open(STAMP, 'w') as f:
         f.write(_flag_stamp())
     if verbose:
-        print(f'built {LIB}', file=sys.stderr)
+        print(f'built {LIB} and {MEDIA_LIB}', file=sys.stderr)
     return LIB
 
 

@@ -1,8 +1,12 @@
-"""Integer / layout side of `mreserve.preprocess` (mreserve/preprocess.py:463-551): what turns decoded media into the
-arrays `MerlotReserve.embed_video` takes.  Media decoding itself (ffmpeg, librosa mel spectrograms, TF image resizing:
-preprocess.py:27-460) is out of scope: frames arrive here as float arrays already at the target resolution, spectrograms
-as [3, 60, 65] arrays.
+"""`mreserve.preprocess` (mreserve/preprocess.py:121-156, 247-271, 463-551): what turns decoded media into the arrays
+`MerlotReserve.embed_video` takes.  File decoding (ffmpeg / ffprobe) and black-bar trimming (preprocess.py:27-118) are out of
+scope; the two numeric transforms behind them run on the GPU (merlot_reserve_amd.media): uint8 frames of any size become
+patches, waveforms become log-mel spectrograms.  Frames that already are float arrays at the target resolution, ready
+patches and ready [3, 60, 65] spectrograms are taken as before.
 
+  make_spectrogram(s)            preprocess.py:121-156   log-mel of a 5 s waveform, three [60, 65] clips
+  segments_from_decoded          preprocess.py:247-271   the array half of video_to_segments
+  preprocess_image_to_patches    preprocess.py:464-481   resize_and_pad (bilinear, antialiased) + space_to_depth
   patchify                       preprocess.py:478-479   tf.nn.space_to_depth(img, 16) + reshape -> [h*w, 768], patch vector
                                                           order (dy, dx, c) -- the same order as pretrain/dataloader.py:83-84
   preprocess_video               preprocess.py:482-551   token / sub-segment streams, bit-exact
@@ -31,9 +35,93 @@ def __getattr__(name):
 
 def video_to_segments(*args, **kwargs):
     """mreserve/preprocess.py:352-460 decodes a video file with ffmpeg / librosa into frames and mel spectrograms: media
-    decoding is outside this package -- pass decoded arrays to preprocess_video."""
-    raise NotImplementedError('video decoding (ffmpeg / librosa) is out of scope: build the segment dicts from decoded frames '
-                              "('frame' or 'patches') and spectrograms ('spectrogram' [3, 60, 65]) and call preprocess_video")
+    decoding is outside this package -- pass the decoded frames and waveform to segments_from_decoded."""
+    raise NotImplementedError('video decoding (ffmpeg) is out of scope: decode the frames (uint8 [n, H, W, 3]) and the mono 22050 Hz '
+                              'waveform yourself, call segments_from_decoded(frames, waveform) and then preprocess_video')
+
+
+def _is_u8(x):
+    import torch
+    return (x.dtype == torch.uint8) if isinstance(x, torch.Tensor) else (np.asarray(x).dtype == np.uint8)
+
+
+def _on_device(x):
+    import torch
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def _host(x):
+    import torch
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else x
+
+
+def make_spectrograms(waveforms, playback_speed=1, sr=22050, pad_size=2, device=None):
+    """Batched make_spectrogram: waveforms float32 [n, L] -> [n, 3, 60, 65], all rows in one launch.  numpy unless `device` is given (then a
+    float32 tensor there)."""
+    from . import media
+    if playback_speed != 1:
+        raise NotImplementedError('only playback_speed=1 (no fast forwarding) is supported')
+    if sr != media.SR:
+        raise NotImplementedError(f'the spectrogram geometry is fixed to {media.SR} Hz, got sr={sr}')
+    shape = tuple(waveforms.shape)
+    if len(shape) != 2:
+        raise ValueError(f'waveforms must be [n, L], got {shape}')
+    seq_size = 60
+    T = media.logmel_frames(shape[1])
+    if T != seq_size * 3 + pad_size * 4:                                                      # preprocess.py:148-149
+        raise ValueError("provided mel spectrogram {}. target size: {}".format((T, 65), (seq_size * 3 + pad_size * 4, 65)))
+    if not _on_device(waveforms):
+        waveforms = np.asarray(_host(waveforms), dtype=np.float32)
+    log_mel = media.logmel(waveforms, playback_speed=float(playback_speed), device=device)
+    starts = [pad_size, 2 * pad_size + seq_size, 3 * pad_size + 2 * seq_size]                # preprocess.py:151-155
+    import torch
+    specs = torch.stack([log_mel[:, a:a + seq_size] for a in starts], 1)
+    return specs if device is not None else specs.cpu().numpy()
+
+
+def make_spectrogram(waveform, playback_speed=1, sr=22050, pad_size=2, device=None):
+    """preprocess.py:121-156: the log-mel spectrogram of one segment's waveform with the pretraining parameters, cut into three [60, 65]
+    clips with gaps of pad_size rows -> [3, 60, 65]."""
+    return make_spectrograms(waveform[None], playback_speed=playback_speed, sr=sr, pad_size=pad_size, device=device)[0]
+
+
+def preprocess_image_to_patches(img, output_grid_size, device=None):
+    """preprocess.py:464-481: a uint8 [H, W, 3] image of any size -> [h1*w1, 768] float32 patches (scaled to fit, zero-padded)."""
+    from . import media
+    h1, w1 = output_grid_size
+    assert h1 <= 24, "we didn't pretrain on anything bigger than 24x24 or 18x32"
+    assert w1 <= 32, "we didn't pretrain on anything bigger than 24x24 or 18x32"
+    out = media.frames_to_patches(img, (h1, w1), device=device)
+    return out if device is not None else out.cpu().numpy()
+
+
+def segments_from_decoded(frames, waveform, sr=22050, time_interval=5.0, segment_start_time=0.0, device=None):
+    """The array half of video_to_segments (preprocess.py:247-271): frames [n, H, W, 3] (one per segment, taken at its middle) and the mono
+    waveform of the clip -> the reference's list of dicts ('start_time', 'end_time', 'mid_time', 'frame', 'spectrogram', 'idx').  The waveform
+    is cast to float32, divided by max(|w|.max(), 1), zero-padded to the last segment's end and cut at int(sr * start) : int(sr * end); all
+    segments' spectrograms come from one launch."""
+    n = len(frames)
+    times, st = [], segment_start_time
+    for _ in range(n):
+        et = st + time_interval
+        times.append({'start_time': st, 'end_time': et, 'mid_time': (st + et) / 2.0})
+        st = et
+    if n == 0:
+        return times
+    waveform = np.asarray(_host(waveform)).astype('float32')
+    waveform = waveform / np.float32(max(np.abs(waveform).max() if waveform.size else 0.0, 1.0))
+    desired_final_frame = int(sr * max(t['end_time'] for t in times))
+    if waveform.size < desired_final_frame:
+        waveform = np.concatenate([waveform, np.zeros(desired_final_frame - waveform.size, dtype=np.float32)], 0)
+    cuts = [waveform[int(sr * t['start_time']):int(sr * t['end_time'])] for t in times]
+    if len({len(c) for c in cuts}) != 1:
+        raise ValueError(f'segments of unequal length {sorted({len(c) for c in cuts})}: choose time_interval and segment_start_time so that sr * time is whole')
+    specs = make_spectrograms(np.stack(cuts), playback_speed=1, sr=sr, device=device)
+    for i, (frame_i, ts_i) in enumerate(zip(frames, times)):
+        ts_i['frame'] = frame_i
+        ts_i['spectrogram'] = specs[i]
+        ts_i['idx'] = i
+    return times
 
 
 def patchify(img, output_grid_size, P=16):
@@ -45,15 +133,46 @@ def patchify(img, output_grid_size, P=16):
     return img.reshape(h1, P, w1, P, 3).transpose(0, 2, 1, 3, 4).reshape(h1 * w1, P * P * 3)
 
 
-def preprocess_video(video_segments, output_grid_size, encoder=None, verbose=False):
-    """preprocess.py:482-551.  Each segment: 'frame' ([H, W, 3] float at output resolution, or 'patches' [h*w, 768]
-    already patchified), 'spectrogram' [3, 60, 65], 'text' (str -- needs `encoder` -- or a list of token ids),
-    'use_text_as_input' (default True).  Returns images [n, h*w, 768], audio_clips [3n, 60, 65], tokens [160] int32,
-    subseg_idxs [160] int32."""
+def _images_on_device(video_segments, output_grid_size, dev):
+    """[n, h*w, 768] float32 on `dev`: uint8 frames through the resize kernel (one launch per frame size), everything else copied."""
+    import torch
+    from . import media
+    h1, w1 = output_grid_size
+    assert h1 <= 24 and w1 <= 32, "we didn't pretrain on anything bigger than 24x24 or 18x32"      # preprocess.py:474-475
+    images = torch.empty((len(video_segments), h1 * w1, 768), dtype=torch.float32, device=dev)
+    groups = {}
+    for i, s in enumerate(video_segments):
+        if 'patches' in s:
+            images[i] = torch.as_tensor(s['patches']).to(device=dev, dtype=torch.float32)
+        elif _is_u8(s['frame']):
+            groups.setdefault(tuple(s['frame'].shape), []).append(i)
+        else:
+            images[i] = torch.from_numpy(patchify(_host(s['frame']), output_grid_size)).to(dev)
+    for idx in groups.values():
+        fr = [video_segments[i]['frame'] for i in idx]
+        batch = torch.stack([f.to(dev) for f in fr]) if isinstance(fr[0], torch.Tensor) else np.stack(fr)
+        images[torch.tensor(idx, device=dev)] = media.frames_to_patches(batch, output_grid_size, device=dev)
+    return images
+
+
+def preprocess_video(video_segments, output_grid_size, encoder=None, verbose=False, *, device=None):
+    """preprocess.py:482-551.  Each segment: 'frame' (uint8 [H, W, 3] of any size -- resized on the GPU --, or [H, W, 3] float at output
+    resolution, or 'patches' [h*w, 768] already patchified), 'spectrogram' [3, 60, 65] or 'waveform' (float32 [110250], 5 s at 22050 Hz --
+    log-mel on the GPU), 'text' (str -- needs `encoder` -- or a list of token ids), 'use_text_as_input' (default True).  Returns images
+    [n, h*w, 768], audio_clips [3n, 60, 65], tokens [160] int32, subseg_idxs [160] int32; images and audio_clips as numpy arrays, or with
+    `device` as float32 tensors there (embed_video takes both)."""
     if len(video_segments) > 8:
         raise ValueError('We only support videos of at most 8 segments right now')             # preprocess.py:497-498
-    images = np.stack([np.asarray(s['patches'], dtype=np.float32) if 'patches' in s else patchify(s['frame'], output_grid_size)
-                       for s in video_segments])
+    gpu_images = device is not None or any('patches' not in s and (_is_u8(s['frame']) or _on_device(s['frame'])) for s in video_segments)
+    if gpu_images:
+        import torch
+        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        images = _images_on_device(video_segments, output_grid_size, dev)
+        if device is None:
+            images = images.cpu().numpy()
+    else:
+        images = np.stack([np.asarray(s['patches'], dtype=np.float32) if 'patches' in s else patchify(s['frame'], output_grid_size)
+                           for s in video_segments])
     subseg_idxs, audio_clips, tokens_out = [], [], []
     for i, segm_i in enumerate(video_segments):
         if segm_i.get('use_text_as_input', True):
@@ -72,7 +191,12 @@ def preprocess_video(video_segments, output_grid_size, encoder=None, verbose=Fal
             subseg_idxs.extend([i * 3] * len(txt_tok))
             tokens_out.extend(txt_tok)
         else:
-            audio_clips.append(np.asarray(segm_i['spectrogram'], dtype=np.float32))
+            if 'spectrogram' not in segm_i and 'waveform' in segm_i:
+                audio_clips.append(None)                                      # filled below: every waveform of the video in one launch
+            elif _on_device(segm_i['spectrogram']):
+                audio_clips.append(segm_i['spectrogram'])
+            else:
+                audio_clips.append(np.asarray(segm_i['spectrogram'], dtype=np.float32))
             tokens_out.extend([AUDIOSPAN] * 18)                               # 6 audio tokens per sub-segment
             subseg_idxs.extend((i * 3 + np.arange(18) // 6).tolist())
     if len(tokens_out) >= 160:
@@ -82,5 +206,19 @@ def preprocess_video(video_segments, output_grid_size, encoder=None, verbose=Fal
     while len(tokens_out) < 160:
         tokens_out.append(0)
         subseg_idxs.append(-1)
-    return {'images': images, 'audio_clips': np.stack(audio_clips).reshape(-1, 60, 65),
+    waves = [i for i, a in enumerate(audio_clips) if a is None]
+    if waves:
+        wv = [video_segments[i]['waveform'] for i in waves]
+        import torch
+        wv = torch.stack(wv) if isinstance(wv[0], torch.Tensor) else np.stack([np.asarray(w, dtype=np.float32) for w in wv])
+        for i, spec in zip(waves, make_spectrograms(wv, device=device)):
+            audio_clips[i] = spec
+    if device is not None or any(_on_device(a) for a in audio_clips):
+        import torch
+        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        audio = torch.stack([torch.as_tensor(a).to(device=dev, dtype=torch.float32) for a in audio_clips]).reshape(-1, 60, 65)
+        audio_clips = audio if device is not None else audio.cpu().numpy()
+    else:
+        audio_clips = np.stack(audio_clips).reshape(-1, 60, 65)
+    return {'images': images, 'audio_clips': audio_clips,
             'tokens': np.array(tokens_out, dtype=np.int32), 'subseg_idxs': np.array(subseg_idxs, dtype=np.int32)}
