@@ -16,9 +16,8 @@ import torch
 
 from . import ops
 from .config import Dims
-from .planner import VOCAB, build_plan, static_tables
-
-BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
+from .planner import VOCAB, audio_tables, build_plan, span_rot_table, vit_tables
+from .towers import BF16, F32, I32, PooledTower, TowerState, cls_view, encoder_forward, layer_names
 
 
 def side_stream_disabled():
@@ -27,49 +26,12 @@ def side_stream_disabled():
     return os.environ.get('MR_NO_SIDE_STREAM') == '1'
 
 
-class _LayerRing:
-    """buffers[l % len(buffers)] for every layer l: what a forward-only TowerState keeps in place of one buffer per layer."""
-
-    def __init__(self, buffers):
-        self.buffers = buffers
-
-    def __getitem__(self, l):
-        return self.buffers[l % len(self.buffers)]
-
-
-class TowerState:
-    """Saved activations of one TransformerEncoder (modeling.py:283-376) over M = nseq*S rows.
-    saved=False (a forward-only program on ONE stream): nothing is kept for a backward -- every layer writes the same one layer's worth of
-    buffers (the residual stream alternates between two), and hpre does not exist."""
-
-    def __init__(self, M, H, L, nseq, S, dev, dtype=BF16, keep_hpre=None, saved=True):
-        nh = H // 64
-        z = lambda *s: torch.zeros(*s, dtype=dtype, device=dev)
-        f = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
-        self.M, self.H, self.L, self.nseq, self.S = M, H, L, nseq, S
-        self.xin, self.xf = z(M, H), z(M, H)
-        self.stats = f(2 * L + 2, 2, M)       # [ln index][mean|rstd][row]; index 0 = pre_ln, 1+2l / 2+2l = layer l, last = final
-        if not saved:
-            self.X = _LayerRing([z(M, H), z(M, H)])
-            self.ln1, self.ln2, self.xmid, self.att = (_LayerRing([z(M, H)]) for _ in range(4))
-            self.qkv, self.hact, self.hpre = _LayerRing([z(M, 3 * H)]), _LayerRing([z(M, 4 * H)]), None
-            self.lse = _LayerRing([f(nseq, nh, S)])
-            return
-        self.X = z(L + 1, M, H)
-        self.ln1, self.ln2, self.xmid, self.att = z(L, M, H), z(L, M, H), z(L, M, H), z(L, M, H)
-        self.qkv = z(L, M, 3 * H)
-        self.hact = z(L, M, 4 * H)
-        keep_hpre = dtype == BF16 if keep_hpre is None else keep_hpre
-        self.hpre = z(L, M, 4 * H) if keep_hpre else None           # gelu'(pre-activation), only kept for backward
-        self.lse = f(L, nseq, nh, S)
-
-
 class TowerEngine:
     """What every program built from TransformerEncoder towers shares (pretraining step, VCR finetuning step): the
-    encoder forward / hand-written backward over a TowerState, the CLS head + attention pool of the vision / audio
-    towers, the two scratch sets (main / side stream) and the device copies of the per-batch plan.
+    encoder forward (towers.encoder_forward) / hand-written backward over a TowerState, the backward stages of the vision / audio
+    input towers (towers.PooledTower), the two scratch sets (main / side stream) and the device copies of the per-batch plan.
     Subclasses set: self.p (ParamStore), self.W / self.G (weight / gradient views), self.dev, self.dtype, self.fwd_only, self.side_stream,
-    self.tables (static device tables: '{vit,audio}_rot', '{vit,audio}_pool_rows' of the towers the program has),
+    self.vision / self.audio (the PooledTowers the program has; self.tv / self.ta name their TowerStates),
     self.sc_main / self.sc_side / self.cur (via _make_scratch), self.plan_dev / _plan_caps / _plan_views / plan_frozen."""
 
     def _make_scratch(self, Ms, Gs, Ps, H, nh):
@@ -113,7 +75,6 @@ class TowerEngine:
         sc.tower_ln_ws = [ln_ws() for _ in range(2)]
         sc.tower_cs_ws = [ops.colsum_workspace(H, dev) for _ in range(6)]
         sc.d_pool_q, sc.d_pool_po, sc.d_pool_qin = z(Gs, H), z(Gs, H), z(Gs, H)
-        sc.d_k, sc.d_v = z(Ms, H), z(Ms, H)                    # CLS rows stay zero
         sc.Dpatch = z(Ps, H)
         return sc
 
@@ -184,11 +145,6 @@ class TowerEngine:
             if not self.fwd_only:
                 self.cur = self.sc_main
 
-    def _unpad_csr(self, nseq, S):
-        rows = (np.arange(nseq)[:, None] * S + 1 + np.arange(S - 1)[None]).reshape(-1).astype(np.int32)
-        indptr = np.arange(len(rows) + 1, dtype=np.int32)
-        return torch.as_tensor(indptr).to(self.dev), torch.as_tensor(rows).to(self.dev)
-
     # ------------------------------------------------------------------------------------------ plan upload
     def set_plan(self, plan):
         """Copy the host plan into ONE persistent device buffer (same addresses every step: graph-capturable) through a ring
@@ -242,34 +198,7 @@ class TowerEngine:
         return self.tj.M + self.ts.M + 64
 
     # ------------------------------------------------------------------------------------------ encoder
-    def _names(self, prefix, l):
-        p = f'{prefix}/layer_{l:02d}'
-        return dict(g1=f'{p}/pre_attn_ln/scale', b1=f'{p}/pre_attn_ln/bias', wqkv=f'{p}/attention_layer/qkv/kernel',
-                    bqkv=f'{p}/attention_layer/qkv/bias', wo=f'{p}/attention_layer/attn_proj/kernel',
-                    g2=f'{p}/pre_mlp_ln/scale', b2=f'{p}/pre_mlp_ln/bias', w1=f'{p}/mlp_layer/intermediate/kernel',
-                    bb1=f'{p}/mlp_layer/intermediate/bias', w2=f'{p}/mlp_layer/out/kernel')
-
-    def encoder_forward(self, st, prefix, rot, code, dense_mask=None):
-        """TransformerEncoder body (modeling.py:360-366) on st.xin (CLS row already in place) -> st.xf.
-        dense_mask: uint8 [nseq, S, S] (!= 0 = allowed) -- ANY attention mask (modeling.py:303, 350-356) instead of the position codes; the
-        attention then runs on the plain dense-mask kernels, forward here and backward in encoder_backward (round 6: a correctness path)."""
-        W, H, nh = self.W, st.H, st.H // 64
-        ops.layernorm_fwd(st.xin, W[f'{prefix}/pre_ln/scale'], W[f'{prefix}/pre_ln/bias'], st.X[0], st.stats[0, 0], st.stats[0, 1])
-        for l in range(st.L):
-            n = self._names(prefix, l)
-            x = st.X[l]
-            ops.layernorm_fwd(x, W[n['g1']], W[n['b1']], st.ln1[l], st.stats[1 + 2 * l, 0], st.stats[1 + 2 * l, 1])
-            self.fgemm(st.ln1[l], n['wqkv'], st.qkv[l], bias=W[n['bqkv']], rot_tab=rot, rot_cols=2 * H)
-            if dense_mask is not None:
-                ops.attention_fwd_dense_mask(st.qkv[l], dense_mask, st.att[l], st.nseq, st.S, nh)
-            else:
-                ops.attention_fwd(st.qkv[l], code, st.att[l], st.lse[l], st.nseq, st.S, nh)
-            self.fgemm(st.att[l], n['wo'], st.xmid[l], residual=x)
-            ops.layernorm_fwd(st.xmid[l], W[n['g2']], W[n['b2']], st.ln2[l], st.stats[2 + 2 * l, 0], st.stats[2 + 2 * l, 1])
-            self.fgemm(st.ln2[l], n['w1'], st.hact[l], bias=W[n['bb1']], act=ops.ACT_GELU, c2=None if st.hpre is None else st.hpre[l])
-            self.fgemm(st.hact[l], n['w2'], st.X[l + 1], residual=st.xmid[l])
-        k = 2 * st.L + 1
-        ops.layernorm_fwd(st.X[st.L], W[f'{prefix}/final_ln/scale'], W[f'{prefix}/final_ln/bias'], st.xf, st.stats[k, 0], st.stats[k, 1])
+    encoder_forward = encoder_forward       # (towers.py; the engine is its `eng`)
 
     def _wgrad_group(self, M, H):
         """Layers whose weight gradients share one grouped launch of the one-tile-per-workgroup TN kernel (csrc/gemm3.hip): the count
@@ -325,7 +254,7 @@ class TowerEngine:
         self._flush_tower_reductions(tr)
         jobs = None if self.dtype == F32 else []      # (fp32: immediate reductions)
         for l in reversed(range(st.L)):
-            n = self._names(prefix, l)
+            n = layer_names(prefix, l)
             T_q, T_h = T_qs[len(done_layers)], T_hs[len(done_layers)]
             Dmid, Dnext = free.pop(), free.pop()
             gi = len(done_layers)               # position in the weight-gradient group: its own partial-row workspaces
@@ -368,92 +297,12 @@ class TowerEngine:
                        G[f'{prefix}/pre_ln/scale'], G[f'{prefix}/pre_ln/bias'])
         return Dcur
 
-    # ------------------------------------------------------------------------------------------ CLS tower head + pool
-    def _cls_view(self, t, nseq, S):
-        return t.view(nseq, S * t.shape[1])[:, :t.shape[1]]
-
-    def _tower_with_pool_forward(self, st, prefix_t, prefix_pool, rot, pool_rows, qin, q, k, v, po, probs, out_seq, out_cls):
-        W, nh = self.W, st.H // 64
-        ops.fill_rows(W[f'{prefix_t}/cls'], st.xin, st.nseq, st.S, 0)
-        self.encoder_forward(st, prefix_t, rot, None)
-        ops.rows_mean_fwd(st.xf, pool_rows, qin)
-        # the CLS head and the pool's query projection are independent small GEMMs (64 / 1152 rows): handed over as a group -- ONE launch when both fall to
-        # the small-problem kernel (tiny configs); at base / large size the 1152-row query projection is claimed by the few-tile kernel (gemm5_wanted, csrc/gemm_route.cpp)
-        # and the library launches the two separately
-        self.fgemm_grouped([(self._cls_view(st.xf, st.nseq, st.S), f'{prefix_t}/cls_proj/kernel', out_cls, dict(bias=W[f'{prefix_t}/cls_proj/bias'])),
-                            (qin, f'{prefix_pool}/query/kernel', q, dict(bias=W[f'{prefix_pool}/query/bias']))])
-        self.fgemm(st.xf, f'{prefix_pool}/key/kernel', k, bias=W[f'{prefix_pool}/key/bias'])
-        self.fgemm(st.xf, f'{prefix_pool}/value/kernel', v, bias=W[f'{prefix_pool}/value/bias'])
-        ops.poolattn_fwd(q, k, v, pool_rows, po, probs, nh)
-        self.fgemm(po, f'{prefix_pool}/out/kernel', out_seq, bias=W[f'{prefix_pool}/out/bias'])
-
-    def _tower_with_pool_backward(self, st, prefix_t, prefix_pool, rot, pool_rows, qin, q, k, v, po, probs, d_seq, d_cls, D,
-                                  layer_done=None, tr=None):
-        """d_seq: grad wrt the pooled sequence output; d_cls: grad wrt the cls output.  Returns D = grad wrt st.xin."""
-        W, G, nh, M = self.W, self.G, st.H // 64, st.M
-        Gn = qin.shape[0]
-        d_po, d_q, d_qin = self.cur.d_pool_po[:Gn], self.cur.d_pool_q[:Gn], self.cur.d_pool_qin[:Gn]
-        d_k, d_v = self.cur.d_k[:M], self.cur.d_v[:M]
-        # the small weight gradients of the head (pool out / query projections, cls_proj: K = 1152 / 1152 / 64 rows) feed nothing in this
-        # backward: they leave the chain of data gradients and run as ONE grouped launch at its end
-        small_wgrads = []
-        defer = self.dtype == BF16
-
-        def wgrad(x, dy, out):
-            if defer:
-                small_wgrads.append(self.gemm_args(x, dy, out, transA=True))
-            else:
-                self.gemm(x, dy, out, transA=True)
-        self._t_colsum(tr, d_seq, G[f'{prefix_pool}/out/bias'])
-        wgrad(po, d_seq, G[f'{prefix_pool}/out/kernel'])
-        self.gemm(d_seq, W[f'{prefix_pool}/out/kernel'], d_po, transB=True)
-        ops.poolattn_bwd(q, k, v, pool_rows, probs, d_po, d_q, d_k, d_v, nh)
-        self._t_colsum(tr, d_q, G[f'{prefix_pool}/query/bias'])
-        wgrad(qin, d_q, G[f'{prefix_pool}/query/kernel'])
-        self.gemm(d_q, W[f'{prefix_pool}/query/kernel'], d_qin, transB=True)
-        self._t_colsum(tr, d_k, G[f'{prefix_pool}/key/bias'])
-        self.gemm(d_k, W[f'{prefix_pool}/key/kernel'], D, transB=True)
-        self._t_colsum(tr, d_v, G[f'{prefix_pool}/value/bias'])
-        self.gemm(d_v, W[f'{prefix_pool}/value/kernel'], D, transB=True, residual=D)
-        # the key / value weight gradients (K = all M tokens) ride in the encoder's first grouped weight-gradient launch
-        extra = [(st.xf, d_k, G[f'{prefix_pool}/key/kernel']), (st.xf, d_v, G[f'{prefix_pool}/value/kernel'])]
-        ops.rows_mean_bwd(d_qin, pool_rows, D)
-        # cls head
-        cls_in = self._cls_view(st.xf, st.nseq, st.S)
-        self._t_colsum(tr, d_cls, G[f'{prefix_t}/cls_proj/bias'])
-        wgrad(cls_in, d_cls, G[f'{prefix_t}/cls_proj/kernel'])
-        Dc = self._cls_view(D, st.nseq, st.S)
-        self.gemm(d_cls, W[f'{prefix_t}/cls_proj/kernel'], Dc, transB=True, residual=Dc)
-        if small_wgrads:
-            ops.gemm_grouped(small_wgrads)
-        D = self.encoder_backward(st, prefix_t, rot, None, D, layer_done=layer_done, tr=tr, extra_wgrads=extra)
-        ops.sum_rows_strided(D, st.nseq, st.S, 0, G[f'{prefix_t}/cls'])
-        return D
-
     # ------------------------------------------------------------------------------------------ input-tower backward stages
     def backward_stage_audio(self):
-        d, G, ta, t = self.d, self.G, self.ta, self.tables
-        tr = self._begin_tower_reductions()
-        Da = self._tower_with_pool_backward(ta, 'audio_encoder/transformer', 'audio_encoder/seq_attnpool', t['audio_rot'],
-                                            t['audio_pool_rows'], self.a_qin, self.a_q, self.a_k, self.a_v, self.a_po,
-                                            self.a_probs, self.d_audio_seq, self.d_a_cls, self.Da, tr=tr)
-        Dp = self.cur.Dpatch[:d.Na * d.a_len]
-        ops.segment_sum([Da], self.unpad_a[0], self.unpad_a[1], Dp)
-        self._t_colsum(tr, Dp, G['audio_encoder/embedding/bias'])
-        self._flush_tower_reductions(tr)
-        self.gemm(self._audio2d, Dp, G['audio_encoder/embedding/kernel'], transA=True)
+        self.audio.backward(self)
 
     def backward_stage_vision(self, layer_done=None):
-        d, G, tv, t = self.d, self.G, self.tv, self.tables
-        tr = self._begin_tower_reductions()
-        Dv = self._tower_with_pool_backward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', t['vit_rot'],
-                                            t['vit_pool_rows'], self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po,
-                                            self.v_probs, self.d_imgs_seq, self.d_v_cls, self.Dv, layer_done=layer_done, tr=tr)
-        Dp = self.cur.Dpatch[:d.Nv * d.hw]
-        ops.segment_sum([Dv], self.unpad_v[0], self.unpad_v[1], Dp)
-        self._t_colsum(tr, Dp, G['vision_encoder/embedding/bias'])
-        self._flush_tower_reductions(tr)
-        self.gemm(self._images2d, Dp, G['vision_encoder/embedding/kernel'], transA=True)
+        self.vision.backward(self, layer_done)
 
 
 class PretrainEngine(TowerEngine):
@@ -474,12 +323,15 @@ class PretrainEngine(TowerEngine):
         self.G = params.g if dtype == BF16 else getattr(params, 'g32', None)
         hp = train
         dev, H = self.dev, d.H
-        self.tables = {k: torch.as_tensor(v).to(dev) for k, v in static_tables(d).items()}
+        self.tables = {'span_rot': torch.as_tensor(span_rot_table(d.span_len)).to(dev)}
         z = lambda *s: torch.zeros(*s, dtype=dtype, device=dev)
         f = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
 
-        self.tv = TowerState(d.Nv * d.Sv, H, d.Lv, d.Nv, d.Sv, dev, dtype, hp)
-        self.ta = TowerState(d.Na * d.Sa, H, d.La, d.Na, d.Sa, dev, dtype, hp)
+        # vision tower (modeling.py:379-430) and audio tower (:433-476), each with its CLS head and attention pool
+        self.vision = PooledTower('vision_encoder', d.Nv, d.hw, d.pp3, d.Lv, H, vit_tables(d.gh, d.gw, d.pr, d.Nv), dev, dtype, train, keep_hpre=hp)
+        self.audio = PooledTower('audio_encoder', d.Na, d.a_len, d.a_patch * 65, d.La, H, audio_tables(d.a_len, d.a_pool, d.Na), dev, dtype, train,
+                                 pad_input=True, keep_hpre=hp)
+        self.tv, self.ta = self.vision.st, self.audio.st
         self.tj = TowerState(d.Nj * d.Sj, H, d.Lj, d.Nj, d.Sj, dev, dtype, hp)
         if not d.do_rotary:                 # d pe: position p sums rows p, Sj + p, 2 Sj + p, ... of the tower-input gradient (a static segment list)
             idx = (np.arange(d.Nj)[None, :] * d.Sj + np.arange(d.Sj)[:, None]).reshape(-1).astype(np.int32)
@@ -487,18 +339,6 @@ class PretrainEngine(TowerEngine):
         self.ts = TowerState(d.Ns * d.Ss, H, d.Ls, d.Ns, d.Ss, dev, dtype, hp)
         Mmax = max(t.M for t in (self.tv, self.ta, self.tj, self.ts))
 
-        # attention pools
-        self.Gv, self.Ga = d.Nv * d.hw4, d.Na * d.a_tok
-        self.v_qin, self.v_q, self.v_po, self.imgs_seq = z(self.Gv, H), z(self.Gv, H), z(self.Gv, H), z(self.Gv, H)
-        self.v_k, self.v_v = z(self.tv.M, H), z(self.tv.M, H)
-        self.v_probs = f(self.Gv, d.nh, d.pr * d.pr)
-        self.v_cls = z(d.Nv, H)
-        self.a_pad_K = (d.a_patch * 65 + 7) // 8 * 8
-        self.a_in = z(d.Na * d.a_len, self.a_pad_K)
-        self.a_qin, self.a_q, self.a_po, self.audio_seq = z(self.Ga, H), z(self.Ga, H), z(self.Ga, H), z(self.Ga, H)
-        self.a_k, self.a_v = z(self.ta.M, H), z(self.ta.M, H)
-        self.a_probs = f(self.Ga, d.nh, d.a_pool)
-        self.a_cls = z(d.Na, H)
         self.hj = z(self.tj.M, H)
         self.s_cls = z(d.Ns, H)
 
@@ -567,21 +407,18 @@ class PretrainEngine(TowerEngine):
         if self.fwd_only:
             return
         # backward scratch
-        self.Dv, self.Da, self.Dj, self.Ds = z(self.tv.M, H), z(self.ta.M, H), z(self.tj.M, H), z(self.ts.M, H)
-        self.d_v_cls, self.d_s_cls = z(d.Nv, H), z(d.Ns, H)
+        self.Dj, self.Ds = z(self.tj.M, H), z(self.ts.M, H)
+        self.d_s_cls = z(d.Ns, H)
         # Two scratch sets: the audio tower runs on a side stream concurrently with the vision tower (forward and
         # backward), so that one tower's kernels fill the CUs the other leaves idle (partial last rounds of the
         # persistent GEMMs, small kernels).  `self.cur` is the set the ops being ISSUED right now may use.
-        self.sc_main = self._make_scratch(Mmax, max(self.Gv, self.Ga), max(d.Nv * d.hw, d.Na * d.a_len), H, d.nh)   # also serves audio when issued in line
-        self.sc_side = self._make_scratch(self.ta.M, self.Ga, d.Na * d.a_len, H, d.nh)
+        Gv, Ga = d.Nv * d.hw4, d.Na * d.a_tok
+        self.sc_main = self._make_scratch(Mmax, max(Gv, Ga), max(d.Nv * d.hw, d.Na * d.a_len), H, d.nh)   # also serves audio when issued in line
+        self.sc_side = self._make_scratch(self.ta.M, Ga, d.Na * d.a_len, H, d.nh)
         self.cur = self.sc_main
         self.dXpool = z(self.n_pool, H)
         self.d_hj = z(self.tj.M, H)
-        self.d_acls_g, self.d_a_cls = z(d.Na, H), z(d.Na, H)
-        self.d_audio_seq, self.d_imgs_seq = z(self.Ga, H), z(self.Gv, H)
-        # static gather lists: patch rows of a [nseq, S] grid without the CLS rows
-        self.unpad_v = self._unpad_csr(d.Nv, d.Sv)
-        self.unpad_a = self._unpad_csr(d.Na, d.Sa)
+        self.d_acls_g = z(d.Na, H)
 
         # (device copies of the per-batch plan -- plan_dev / _plan_caps / _plan_views, set above -- have fixed sizes where
         # possible; index lists are padded to capacity)
@@ -602,34 +439,14 @@ class PretrainEngine(TowerEngine):
         d, W, H = self.d, self.W, self.d.H
         if images.dtype != self.dtype:          # the wire format is bf16 (pretrain/dataloader.py:786-788); the fp32 program casts up, like the
             images, audio_clips = images.to(self.dtype), audio_clips.to(self.dtype)     # reference model's first op (M: x.astype(self.dtype))
-        batch = {'images': images, 'audio_clips': audio_clips}
-        tv, ta, tj, ts = self.tv, self.ta, self.tj, self.ts
-
+        tj, ts = self.tj, self.ts
         # vision tower (main stream) and audio tower (side stream) are independent until the joint tower
-        def audio_fwd():
-            # audio tower (modeling.py:433-476): the stride-2 conv is a GEMM over 2 consecutive hops = 130 inputs
-            audio = batch['audio_clips'].reshape(d.Na * d.a_len, d.a_patch * 65)
-            if self.dtype == BF16:                       # 16-byte rows for the bf16 GEMM (the fp32 GEMM reads 130-wide rows as they are)
-                ops.pad_cols(audio, self.a_in)
-                a_view = self.a_in[:, :d.a_patch * 65]
-            else:
-                a_view = audio
-            self._audio2d = a_view
-            self.fgemm(a_view, 'audio_encoder/embedding/kernel', ta.xin, bias=W['audio_encoder/embedding/bias'], row_map=(d.a_len, d.Sa, 1))
-            self._tower_with_pool_forward(ta, 'audio_encoder/transformer', 'audio_encoder/seq_attnpool', self.tables['audio_rot'],
-                                          self.tables['audio_pool_rows'], self.a_qin, self.a_q, self.a_k, self.a_v, self.a_po,
-                                          self.a_probs, self.audio_seq, self.a_cls)
         main = torch.cuda.current_stream()
         self.side_stream.wait_stream(main)
-        self._on_side(audio_fwd)
-        # vision tower (modeling.py:379-430)
-        images = self._images2d = batch['images'].reshape(d.Nv * d.hw, d.pp3)
-        self.fgemm(images, 'vision_encoder/embedding/kernel', tv.xin, bias=W['vision_encoder/embedding/bias'], row_map=(d.hw, d.Sv, 1))
-        self._tower_with_pool_forward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.tables['vit_rot'],
-                                      self.tables['vit_pool_rows'], self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po,
-                                      self.v_probs, self.imgs_seq, self.v_cls)
+        self._on_side(lambda: self.audio.forward(self, audio_clips.reshape(d.Na * d.a_len, d.a_patch * 65)))
+        self.vision.forward(self, images.reshape(d.Nv * d.hw, d.pp3))
         if d.no_vision:                  # pretrain/pretrain_model.py:61-63: imgs_seq *= 0.0 (the cls output still feeds the contrastive loss)
-            self.imgs_seq.zero_()
+            self.vision.seq.zero_()
         main.wait_stream(self.side_stream)
         emb = W['token_encoder/Embed_0/embedding']
 
@@ -638,18 +455,18 @@ class PretrainEngine(TowerEngine):
             ops.segment_sum([emb], self._pl('span_gather_indptr'), self._pl('span_gather_idx'), ts.xin)
             ops.fill_rows(W['span_encoder/transformer/cls'], ts.xin, ts.nseq, ts.S, 0)
             self.encoder_forward(ts, 'span_encoder/transformer', self.tables['span_rot'], self._pl('span_code'))
-            self.fgemm(self._cls_view(ts.xf, ts.nseq, ts.S), 'span_encoder/transformer/cls_proj/kernel', self.s_cls,
+            self.fgemm(cls_view(ts.xf, ts.nseq, ts.S), 'span_encoder/transformer/cls_proj/kernel', self.s_cls,
                      bias=W['span_encoder/transformer/cls_proj/bias'])
         self.side_stream.wait_stream(main)
         self._on_side(span_fwd)
         # joint tower: one gather assembles [token embeddings | audio spans | vision tokens | zero padding]
-        ops.segment_sum([emb, self.audio_seq, self.imgs_seq], self._pl('joint_gather_indptr'), self._pl('joint_gather_idx'), tj.xin)
+        ops.segment_sum([emb, self.audio.seq, self.vision.seq], self._pl('joint_gather_indptr'), self._pl('joint_gather_idx'), tj.xin)
         if not d.do_rotary:                # pretrain_model.py:146-148 + modeling.py:335-341: no coordinates, x += pe (every position, padding included)
             ops.add_rows_periodic(tj.xin, W['joint_transformer/pe'])          # one launch for all d.Nj sequences
         self.encoder_forward(tj, 'joint_transformer', self._joint_rot(), self._pl('joint_code'))
         self.fgemm(tj.xf, 'head/kernel', self.hj, bias=W['head/bias'])
         ops.segment_sum([self.hj], self._pl('pool_indptr'), self._pl('pool_idx'), self.Xpool)
-        ops.segment_sum([self.a_cls], self._pl('acls_indptr'), self._pl('acls_idx'), self.acls_g)
+        ops.segment_sum([self.audio.cls], self._pl('acls_indptr'), self._pl('acls_idx'), self.acls_g)
         main.wait_stream(self.side_stream)
         # unit-normalise * temperature into the packed buffer E (pretrain_model.py:239-257)
         for src, names, si in self._norm_sections():
@@ -659,7 +476,7 @@ class PretrainEngine(TowerEngine):
 
     def _norm_sections(self):
         n1, n2 = self.sec['i2a_x'][1], self.sec['t2a_x'][1]
-        return [(self.Xpool[:n1], ('i2a_x',), 0), (self.v_cls, ('i2a_y',), 0),
+        return [(self.Xpool[:n1], ('i2a_x',), 0), (self.vision.cls, ('i2a_y',), 0),
                 (self.Xpool[n1:n1 + n2], ('t2a_x',), 1), (self.acls_g, ('t2a_y', 't2a_ye'), 1),
                 (self.Xpool[n1 + n2:], ('s2s_x',), 2), (self.s_cls, ('s2s_y',), 2)]
 
@@ -751,7 +568,7 @@ class PretrainEngine(TowerEngine):
         tv, ta, tj, ts = self.tv, self.ta, self.tj, self.ts
         self.dls.zero_()
         n1, n2 = self.sec['i2a_x'][1], self.sec['t2a_x'][1]
-        dsts = [self.dXpool[:n1], self.d_v_cls, self.dXpool[n1:n1 + n2], self.d_acls_g, self.dXpool[n1 + n2:], self.d_s_cls]
+        dsts = [self.dXpool[:n1], self.vision.d_cls, self.dXpool[n1:n1 + n2], self.d_acls_g, self.dXpool[n1 + n2:], self.d_s_cls]
         for (src, names, si), dst in zip(self._norm_sections(), dsts):
             o, n = self.sec[names[0]][0], sum(self.sec[k][1] for k in names)
             ops.unit_norm_scale_bwd(src, W['contrastive_scales'][si:si + 1], self.inv_norm[o:o + n], self.dE[o:o + n], dst,
@@ -766,10 +583,10 @@ class PretrainEngine(TowerEngine):
             Ds = self.Ds
             Ds.zero_()
             tr = self._begin_tower_reductions()
-            cls_in = self._cls_view(ts.xf, ts.nseq, ts.S)
+            cls_in = cls_view(ts.xf, ts.nseq, ts.S)
             self._t_colsum(tr, self.d_s_cls, G['span_encoder/transformer/cls_proj/bias'])
             self.gemm(cls_in, self.d_s_cls, G['span_encoder/transformer/cls_proj/kernel'], transA=True)
-            self.gemm(self.d_s_cls, W['span_encoder/transformer/cls_proj/kernel'], self._cls_view(Ds, ts.nseq, ts.S), transB=True)
+            self.gemm(self.d_s_cls, W['span_encoder/transformer/cls_proj/kernel'], cls_view(Ds, ts.nseq, ts.S), transB=True)
             Ds = self.encoder_backward(ts, 'span_encoder/transformer', self.tables['span_rot'], self._pl('span_code'), Ds, tr=tr)
             self._flush_tower_reductions(tr)
             ops.sum_rows_strided(Ds, ts.nseq, ts.S, 0, G['span_encoder/transformer/cls'])
@@ -795,11 +612,11 @@ class PretrainEngine(TowerEngine):
         main.wait_stream(self.side_stream)
         # scatter-adds of the joint / span inputs, as segment sums over the planner's inverted lists
         ops.segment_sum([Dj, Ds], self._pl('embT_indptr'), self._pl('embT_idx'), G['token_encoder/Embed_0/embedding'])
-        ops.segment_sum([Dj], self._pl('audT_indptr'), self._pl('audT_idx'), self.d_audio_seq)
-        ops.segment_sum([Dj], self._pl('visT_indptr'), self._pl('visT_idx'), self.d_imgs_seq)
+        ops.segment_sum([Dj], self._pl('audT_indptr'), self._pl('audT_idx'), self.audio.d_seq)
+        ops.segment_sum([Dj], self._pl('visT_indptr'), self._pl('visT_idx'), self.vision.d_seq)
         if d.no_vision:                  # d(imgs_seq * 0) = 0
-            self.d_imgs_seq.zero_()
-        ops.segment_sum([self.d_acls_g], self._pl('aclsT_indptr'), self._pl('aclsT_idx'), self.d_a_cls)
+            self.vision.d_seq.zero_()
+        ops.segment_sum([self.d_acls_g], self._pl('aclsT_indptr'), self._pl('aclsT_idx'), self.audio.d_cls)
 
     def loss_info(self):
         """Host dict like the reference's loss_info (pretrain_model.py:263-303) from the device accumulators."""

@@ -30,10 +30,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .engine import BF16, F32, I32, TowerEngine, TowerState
+from .engine import BF16, F32, I32, PooledTower, TowerEngine, TowerState
 from .optim import AdamStepState, BucketSchedule, lr_scale_linearwarmup_lineardecay, vision_cut_buckets
 from .params import VOCAB, ParamStore, decay_finetune, vcr_param_specs
-from .planner import MASK, PADDING, csr_from_pairs, csr_gather, rot_scale_table, rotary_coords_2d
+from .planner import MASK, PADDING, csr_from_pairs, csr_gather, rot_scale_table, rotary_coords_2d, vit_tables
 
 
 class VCRDims:
@@ -138,24 +138,15 @@ class VCREngine(FinetuneEngine):
         dev, H = self.dev, d.H
         z = lambda *s: torch.zeros(*s, dtype=BF16, device=dev)
         f = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
-        self.tv = TowerState(B * d.Sv, H, d.Lv, B, d.Sv, dev, saved=train)
+        self.vision = PooledTower('vision_encoder', B, d.hw, d.pp3, d.Lv, H, vit_tables(d.gh, d.gw, d.pr, B), dev, train=train, saved=train)
+        self.tv = self.vision.st
         self.tj = TowerState(d.n * d.Sj, H, d.Lj, d.n, d.Sj, dev, saved=train)
-        # static tables: ViT rotary / pool rows; joint rotary (text: segment 0, token index 1..T; vision: pooled-grid (h, w),
-        # segment 0 -- identical for every sequence: M:697-720 with token_segment_idx = 0, F:161)
-        vit_rot = torch.from_numpy(rot_scale_table(np.concatenate([np.zeros((1, 2)), rotary_coords_2d(d.gh, d.gw)], 0))).to(dev)
-        pr, h2, w2 = d.pr, d.gh // d.pr, d.gw // d.pr
-        n_, i2, j2, di, dj = np.meshgrid(np.arange(B), np.arange(h2), np.arange(w2), np.arange(pr), np.arange(pr), indexing='ij')
-        vit_pool_rows = torch.from_numpy((n_ * d.Sv + 1 + (i2 * pr + di) * d.gw + j2 * pr + dj).reshape(B * h2 * w2, pr * pr).astype(np.int32)).to(dev)
-        self.tables = {'vit_rot': vit_rot, 'vit_pool_rows': vit_pool_rows}
+        # joint rotary (text: segment 0, token index 1..T; vision: pooled-grid (h, w), segment 0 -- identical for every sequence:
+        # M:697-720 with token_segment_idx = 0, F:161)
         coords = np.zeros((d.Sj, 4))
         coords[:d.T, 3] = (1.0 + np.arange(d.T)) / 1024.0
-        coords[d.T:, :2] = rotary_coords_2d(h2, w2)
+        coords[d.T:, :2] = rotary_coords_2d(d.gh // d.pr, d.gw // d.pr)
         self.joint_rot = torch.from_numpy(rot_scale_table(coords)).to(dev)
-        G = B * d.V
-        self.v_qin, self.v_q, self.v_po, self.imgs_seq = z(G, H), z(G, H), z(G, H), z(G, H)
-        self.v_k, self.v_v = z(self.tv.M, H), z(self.tv.M, H)
-        self.v_probs = f(G, d.nh, pr * pr)
-        self.v_cls = z(B, H)
         self.pooled_h = z(d.n, H)
         self.logits = f(d.n, 8)                       # column 0 = the Dense(1) output
         self.loss_acc = f(2)                          # [loss, is_right]
@@ -169,13 +160,11 @@ class VCREngine(FinetuneEngine):
         bb, ii, jj = np.meshgrid(np.arange(B), np.arange(d.V), np.arange(2 * d.A), indexing='ij')
         ip, ix = csr_from_pairs((bb * d.V + ii).reshape(-1), ((bb * 2 * d.A + jj) * d.Sj + d.T + ii).reshape(-1), B * d.V)
         self.visT = (torch.from_numpy(ip).to(dev), torch.from_numpy(ix).to(dev))
-        self.unpad_v = self._unpad_csr(B, d.Sv)
         self.d_pooled = z(d.n, H)
         self.dlogits = z(d.n, 8)
-        self.Dv, self.Dj = z(self.tv.M, H), z(self.tj.M, H)
-        self.d_imgs_seq, self.d_v_cls = z(G, H), z(B, H)
+        self.Dj = z(self.tj.M, H)
         Mmax = max(self.tv.M, self.tj.M)
-        self.sc_main = self._make_scratch(Mmax, G, B * d.hw, H, d.nh)
+        self.sc_main = self._make_scratch(Mmax, B * d.V, B * d.hw, H, d.nh)
         self.sc_side = self.sc_main                   # single-stream program: the two towers are strictly sequential
         self.cur = self.sc_main
 
@@ -183,12 +172,9 @@ class VCREngine(FinetuneEngine):
         return build_vcr_plan(batch['answers'], self.d)
 
     def forward_device(self, image):
-        d, W, tv, tj = self.d, self.W, self.tv, self.tj
-        self._images2d = image.reshape(d.B * d.hw, d.pp3)
-        self.fgemm(self._images2d, 'vision_encoder/embedding/kernel', tv.xin, bias=W['vision_encoder/embedding/bias'], row_map=(d.hw, d.Sv, 1))
-        self._tower_with_pool_forward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.tables['vit_rot'], self.tables['vit_pool_rows'],
-                                      self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po, self.v_probs, self.imgs_seq, self.v_cls)
-        ops.segment_sum([W['token_encoder/Embed_0/embedding'], self.imgs_seq], self._pl('joint_gather_indptr'), self._pl('joint_gather_idx'), tj.xin)
+        d, W, tj = self.d, self.W, self.tj
+        self.vision.forward(self, image.reshape(d.B * d.hw, d.pp3))
+        ops.segment_sum([W['token_encoder/Embed_0/embedding'], self.vision.seq], self._pl('joint_gather_indptr'), self._pl('joint_gather_idx'), tj.xin)
         self.encoder_forward(tj, 'joint_transformer', self.joint_rot, self._pl('joint_code'))
         ops.segment_sum([tj.xf], self._pl('pool_indptr'), self._pl('pool_idx'), self.pooled_h)
         self.gemm(self.pooled_h, W['proj/kernel'], self.logits, transB=True)          # Dense(1): [n, H] x [1, H]^T -> column 0
@@ -220,7 +206,7 @@ class VCREngine(FinetuneEngine):
         Dj = self.encoder_backward(tj, 'joint_transformer', self.joint_rot, self._pl('joint_code'), self.Dj, tr=tr)
         self._flush_tower_reductions(tr)
         ops.segment_sum([Dj], self._pl('embT_indptr'), self._pl('embT_idx'), G['token_encoder/Embed_0/embedding'])
-        ops.segment_sum([Dj], self.visT[0], self.visT[1], self.d_imgs_seq)
+        ops.segment_sum([Dj], self.visT[0], self.visT[1], self.vision.d_seq)
 
     def loss_info(self):
         return self.info_from(self.loss_acc.tolist())

@@ -30,10 +30,10 @@ import torch
 
 from . import ops
 from .params import VOCAB, _get, param_specs
-from .planner import AUDIOSPAN, PADDING, rot_scale_table, rotary_coords_1d, rotary_coords_2d
+from .planner import AUDIOSPAN, PADDING, audio_tables, rot_scale_table, rotary_coords_1d, rotary_coords_2d, vit_tables
+from .towers import BF16, F32, I32, PooledTower, TowerState, cls_view, encoder_forward
 
 MASK, MASKAUDIO, LTOVPOOL = 3, 4, 6
-BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 
 # ------------------------------------------------------------------------------------------------ coordinates (host)
@@ -164,6 +164,15 @@ class _Module:
     def _empty(self, *shape):
         return torch.empty(*shape, device=self.device, dtype=self.dtype)
 
+    # what the shared tower functions (towers.py) ask of an `eng`: the bound [in, out] weights as they are (transB = False, no split-K
+    # workspace), every member of a group as a launch of its own (as TowerEngine.fgemm_grouped does for fp32)
+    def fgemm(self, a, name, out, **kw):
+        return ops.gemm(a, self.W[name], out, **kw)
+
+    def fgemm_grouped(self, items):
+        for a, name, out, kw in items:
+            self.fgemm(a, name, out, **kw)
+
 
 class TransformerEncoder(_Module):
     """M:283-376"""
@@ -182,11 +191,10 @@ class TransformerEncoder(_Module):
         if is_valid is not None and attention_mask is not None:
             raise ValueError('Provide only one of `is_valid` and `attention_mask` as we can use is_valid to construct attention mask')
         S = L + (1 if self.add_cls_token else 0)
+        st = TowerState(nseq * S, H, self.num_layers, nseq, S, self.device, self.dtype, percall=True,
+                        xin=None if self.add_cls_token else x.reshape(nseq * L, H).contiguous())
         if self.add_cls_token:
-            xin = self._empty(nseq * S, H)
-            xin.view(nseq, S, H)[:, 1:].copy_(x.reshape(nseq, L, H))
-        else:
-            xin = x.reshape(nseq * L, H).contiguous()
+            st.xin.view(nseq, S, H)[:, 1:].copy_(x.reshape(nseq, L, H))
         code = None
         if attention_code is not None:
             code = _np(attention_code, np.int32).reshape(nseq, L)
@@ -200,7 +208,7 @@ class TransformerEncoder(_Module):
                 code = _mask_to_code(m)             # the block form every mask of the model has: one code per position, the fast kernels
             except NotImplementedError:
                 dense = torch.from_numpy(np.ascontiguousarray(m.astype(np.uint8))).to(self.device)      # anything else: mr_attention_fwd_dense_mask
-        xf = self._run(xin, nseq, S, rotary_coords, code, dense_mask=dense)
+        xf = self._run(st, rotary_coords, code, dense_mask=dense)
         info = {}
         if self.add_cls_token:
             info['cls'] = self._cls_proj(xf, nseq, S).reshape(*batch_dims, H)
@@ -210,18 +218,17 @@ class TransformerEncoder(_Module):
         return info
 
     def _cls_proj(self, xf, nseq, S):
-        H, W = self.hidden_size, self.W
-        out = self._empty(nseq, H)
-        ops.gemm(xf.view(nseq, S * H)[:, :H], W[f'{self.prefix}/cls_proj/kernel'], out, bias=W[f'{self.prefix}/cls_proj/bias'])
+        out = self._empty(nseq, self.hidden_size)
+        self.fgemm(cls_view(xf, nseq, S), f'{self.prefix}/cls_proj/kernel', out, bias=self.W[f'{self.prefix}/cls_proj/bias'])
         return out
 
-    def _run(self, xin, nseq, S, rotary_coords, code, dense_mask=None):
-        """xin [nseq*S, H] with the CLS rows (if any) still to be filled; rotary_coords / code WITHOUT the CLS position.
+    def _run(self, st, rotary_coords, code, dense_mask=None):
+        """st.xin [nseq*S, H] with the CLS rows (if any) still to be filled; rotary_coords / code WITHOUT the CLS position.
         Returns final_ln(x) [nseq*S, H]."""
         W, H, p = self.W, self.hidden_size, self.prefix
-        nh, M, dev = H // 64, nseq * S, self.device
+        nseq, S, M, dev = st.nseq, st.S, st.M, self.device
         if self.add_cls_token:
-            ops.fill_rows(W[f'{p}/cls'], xin, nseq, S, 0)
+            ops.fill_rows(W[f'{p}/cls'], st.xin, nseq, S, 0)
             if code is not None:
                 code = np.concatenate([np.zeros((nseq, 1), np.int32), code], 1)  # CLS is always valid (M:321-322)
         if rotary_coords is None:
@@ -231,7 +238,7 @@ class TransformerEncoder(_Module):
                 raise KeyError(f"rotary_coords is None and the parameters hold no '{p}/pe' (learned position embeddings, mreserve/modeling.py:335-341): "
                                'this encoder was initialised with rotary coordinates')
             assert tuple(pe.shape) == (S, H), f'pe has shape {tuple(pe.shape)}, the sequence (with CLS, if any) needs {(S, H)}'
-            ops.add_rows_periodic(xin, pe)
+            ops.add_rows_periodic(st.xin, pe)
             rot = None
         else:
             rc = _np(rotary_coords, np.float64)
@@ -242,44 +249,20 @@ class TransformerEncoder(_Module):
             assert rc.shape[0] in (S, M), 'rotary_coords batch dims must be absent or equal to the batch dims of x'
             rot = torch.from_numpy(rot_scale_table(rc)).to(dev)
         code_t = None if code is None else torch.from_numpy(np.ascontiguousarray(code.reshape(-1))).to(dev)
-        e = self._empty
-        xa, xb, ln, qkv, att, xmid, hid = e(M, H), e(M, H), e(M, H), e(M, 3 * H), e(M, H), e(M, H), e(M, 4 * H)
-        lse = torch.empty(nseq, nh, S, device=dev, dtype=F32) if self.dtype == BF16 else None
-        ops.layernorm_fwd(xin, W[f'{p}/pre_ln/scale'], W[f'{p}/pre_ln/bias'], xa)
-        for l in range(self.num_layers):
-            q = f'{p}/layer_{l:02d}'
-            ops.layernorm_fwd(xa, W[f'{q}/pre_attn_ln/scale'], W[f'{q}/pre_attn_ln/bias'], ln)
-            ops.gemm(ln, W[f'{q}/attention_layer/qkv/kernel'], qkv, bias=W[f'{q}/attention_layer/qkv/bias'], rot_tab=rot, rot_cols=2 * H if rot is not None else 0)
-            if dense_mask is not None:
-                ops.attention_fwd_dense_mask(qkv, dense_mask, att, nseq, S, nh)
-            else:
-                ops.attention_fwd(qkv, code_t, att, lse, nseq, S, nh)
-            ops.gemm(att, W[f'{q}/attention_layer/attn_proj/kernel'], xmid, residual=xa)
-            ops.layernorm_fwd(xmid, W[f'{q}/pre_mlp_ln/scale'], W[f'{q}/pre_mlp_ln/bias'], ln)
-            ops.gemm(ln, W[f'{q}/mlp_layer/intermediate/kernel'], hid, bias=W[f'{q}/mlp_layer/intermediate/bias'], act=ops.ACT_GELU)
-            ops.gemm(hid, W[f'{q}/mlp_layer/out/kernel'], xb, residual=xmid)
-            xa, xb = xb, xa
-        ops.layernorm_fwd(xa, W[f'{p}/final_ln/scale'], W[f'{p}/final_ln/bias'], xb)
-        return xb
+        encoder_forward(self, st, p, rot, code_t, dense_mask=dense_mask)
+        return st.xf
 
 
 class _PooledEncoder(_Module):
-    """Shared tail of VisionTransformer / AudioTransformer: attention pooling with a mean query (M:412-427, 464-472)."""
+    """Shared body of VisionTransformer / AudioTransformer: the tower the training engines run (towers.PooledTower), built per call."""
 
-    def _attnpool(self, xf, key_rows, nseq, S):
-        W, H, p = self.W, self.hidden_size, f'{self.prefix}/seq_attnpool'
-        G = key_rows.shape[0]
-        rows = torch.from_numpy(key_rows).to(self.device)
-        e = self._empty
-        qin, q, k, v, po, out = e(G, H), e(G, H), e(nseq * S, H), e(nseq * S, H), e(G, H), e(G, H)
-        ops.rows_mean_fwd(xf, rows, qin)
-        ops.gemm(qin, W[f'{p}/query/kernel'], q, bias=W[f'{p}/query/bias'])
-        ops.gemm(xf, W[f'{p}/key/kernel'], k, bias=W[f'{p}/key/bias'])
-        ops.gemm(xf, W[f'{p}/value/kernel'], v, bias=W[f'{p}/value/bias'])
-        probs = torch.empty(G, H // 64, key_rows.shape[1], device=self.device, dtype=F32) if self.dtype == BF16 else None
-        ops.poolattn_fwd(q, k, v, rows, po, probs, H // 64)
-        ops.gemm(po, W[f'{p}/out/kernel'], out, bias=W[f'{p}/out/bias'])
-        return out
+    def _tower(self, x, batch_dims, n_in, tables, pad_input=False):
+        """x [N * n_in, K] -> the reference's dict, with the batch dims of the call."""
+        H, N = self.hidden_size, x.shape[0] // n_in
+        t = PooledTower(self.prefix, N, n_in, x.shape[1], self.num_layers, H, tables, self.device, self.dtype, pad_input=pad_input, percall=True)
+        t.forward(self, x.contiguous())
+        return {'cls': t.cls.reshape(*batch_dims, H), 'seq': t.st.xf.view(N, n_in + 1, H)[:, 1:].reshape(*batch_dims, n_in, H),
+                'seq_attnpool': t.seq.reshape(*batch_dims, -1, H)}
 
 
 class VisionTransformer(_PooledEncoder):
@@ -296,21 +279,10 @@ class VisionTransformer(_PooledEncoder):
         *batch_dims, hw, pp3 = x.shape
         assert hw == self.output_grid_h * self.output_grid_w
         assert pp3 == (self.patch_size ** 2) * 3
-        W, H, pr, gw = self.W, self.hidden_size, self.pooling_ratio, self.output_grid_w
+        pr, gw = self.pooling_ratio, self.output_grid_w
         assert self.output_grid_h % pr == 0 and gw % pr == 0
         N = int(np.prod(batch_dims)) if batch_dims else 1
-        S = hw + 1
-        xin = self._empty(N * S, H)
-        ops.gemm(x.reshape(N * hw, pp3), W[f'{self.prefix}/embedding/kernel'], xin, bias=W[f'{self.prefix}/embedding/bias'],
-                 row_map=(hw, S, 1))
-        coords = rotary_coords_2d(self.output_grid_h, gw)
-        xf = self.transformer._run(xin, N, S, coords, None)
-        h2, w2 = self.output_grid_h // pr, gw // pr
-        n, i2, j2, di, dj = np.meshgrid(np.arange(N), np.arange(h2), np.arange(w2), np.arange(pr), np.arange(pr), indexing='ij')
-        key_rows = (n * S + 1 + (i2 * pr + di) * gw + j2 * pr + dj).reshape(N * h2 * w2, pr * pr).astype(np.int32)
-        return {'cls': self.transformer._cls_proj(xf, N, S).reshape(*batch_dims, H),
-                'seq': xf.view(N, S, H)[:, 1:].reshape(*batch_dims, hw, H),
-                'seq_attnpool': self._attnpool(xf, key_rows, N, S).reshape(*batch_dims, h2 * w2, H)}
+        return self._tower(x.reshape(N * hw, pp3), batch_dims, hw, vit_tables(self.output_grid_h, gw, pr, N))
 
 
 class AudioTransformer(_PooledEncoder):
@@ -326,27 +298,11 @@ class AudioTransformer(_PooledEncoder):
         *batch_dims, raw_len, nm = x.shape
         assert nm == 65
         assert raw_len % self.patch_size == 0
-        W, H = self.W, self.hidden_size
         seq_len = raw_len // self.patch_size
         assert seq_len % self.pooling_ratio == 0
         N = int(np.prod(batch_dims)) if batch_dims else 1
-        S, K = seq_len + 1, self.patch_size * 65
-        a = x.reshape(N * seq_len, K)
-        if self.dtype == BF16:                           # 16-byte rows for the bf16 kernels: pad 130 -> 136 columns
-            Kp = (K + 7) // 8 * 8
-            a_pad = self._empty(N * seq_len, Kp)
-            ops.pad_cols(a.contiguous(), a_pad)
-            a = a_pad[:, :K]
-        xin = self._empty(N * S, H)
-        ops.gemm(a, W[f'{self.prefix}/embedding/kernel'], xin, bias=W[f'{self.prefix}/embedding/bias'], row_map=(seq_len, S, 1))
-        coords = rotary_coords_1d(seq_len, True)[:, None] / seq_len
-        xf = self.transformer._run(xin, N, S, coords, None)
-        l2 = seq_len // self.pooling_ratio
-        n, tt, r = np.meshgrid(np.arange(N), np.arange(l2), np.arange(self.pooling_ratio), indexing='ij')
-        key_rows = (n * S + 1 + tt * self.pooling_ratio + r).reshape(N * l2, self.pooling_ratio).astype(np.int32)
-        return {'cls': self.transformer._cls_proj(xf, N, S).reshape(*batch_dims, H),
-                'seq': xf.view(N, S, H)[:, 1:].reshape(*batch_dims, seq_len, H),
-                'seq_attnpool': self._attnpool(xf, key_rows, N, S).reshape(*batch_dims, l2, H)}
+        # 16-byte rows for the bf16 kernels: the tower pads 130 -> 136 columns
+        return self._tower(x.reshape(N * seq_len, self.patch_size * 65), batch_dims, seq_len, audio_tables(seq_len, self.pooling_ratio, N), pad_input=True)
 
 
 class SpanTransformer(_Module):

@@ -50,19 +50,31 @@ def rot_scale_table(coords, rotary_hsize=32, max_freq=10.0):
     return np.stack([s - c, s + c], -1).reshape(*coords.shape[:-1], 2 * nd * de).astype(np.float32)
 
 
-def static_tables(d):
-    """Per-configuration constants: rotary scale tables of the ViT / audio / span encoders (CLS row = coordinate 0,
-    modeling.py:324-326) and the key rows of the two attention pools (modeling.py:419-421, 467)."""
-    t = {}
-    t['vit_rot'] = rot_scale_table(np.concatenate([np.zeros((1, 2)), rotary_coords_2d(d.gh, d.gw)], 0))
-    t['audio_rot'] = rot_scale_table(np.concatenate([np.zeros((1, 1)), rotary_coords_1d(d.a_len)[:, None] / d.a_len], 0))
-    t['span_rot'] = rot_scale_table(np.concatenate([np.zeros((1, 1)), rotary_coords_1d(d.span_len, False)[:, None] / 16.0], 0))
-    pr, h2, w2 = d.pr, d.gh // d.pr, d.gw // d.pr
-    n, i2, j2, di, dj = np.meshgrid(np.arange(d.Nv), np.arange(h2), np.arange(w2), np.arange(pr), np.arange(pr), indexing='ij')
-    t['vit_pool_rows'] = (n * d.Sv + 1 + (i2 * pr + di) * d.gw + j2 * pr + dj).reshape(d.Nv * h2 * w2, pr * pr).astype(np.int32)
-    n, tt, r = np.meshgrid(np.arange(d.Na), np.arange(d.a_tok), np.arange(d.a_pool), indexing='ij')
-    t['audio_pool_rows'] = (n * d.Sa + 1 + tt * d.a_pool + r).reshape(d.Na * d.a_tok, d.a_pool).astype(np.int32)
-    return t
+def _cls_rot(coords):
+    """The rotary scale table of an encoder that prepends a CLS token: its coordinates are 0 (modeling.py:324-326)."""
+    return rot_scale_table(np.concatenate([np.zeros((1, coords.shape[1])), coords], 0))
+
+
+def vit_tables(gh, gw, pr, N):
+    """(rotary scale table [gh gw + 1, 32], key rows of the attention pool [N gh gw / pr^2, pr^2], modeling.py:419-421) of the ViT on N
+    images of gh x gw patches."""
+    h2, w2 = gh // pr, gw // pr
+    n, i2, j2, di, dj = np.meshgrid(np.arange(N), np.arange(h2), np.arange(w2), np.arange(pr), np.arange(pr), indexing='ij')
+    rows = (n * (gh * gw + 1) + 1 + (i2 * pr + di) * gw + j2 * pr + dj).reshape(N * h2 * w2, pr * pr).astype(np.int32)
+    return _cls_rot(rotary_coords_2d(gh, gw)), rows
+
+
+def audio_tables(a_len, a_pool, N):
+    """(rotary scale table [a_len + 1, 32], key rows of the attention pool [N a_len / a_pool, a_pool], modeling.py:467) of the audio
+    encoder on N clips of a_len positions."""
+    n, tt, r = np.meshgrid(np.arange(N), np.arange(a_len // a_pool), np.arange(a_pool), indexing='ij')
+    rows = (n * (a_len + 1) + 1 + tt * a_pool + r).reshape(N * (a_len // a_pool), a_pool).astype(np.int32)
+    return _cls_rot(rotary_coords_1d(a_len)[:, None] / a_len), rows
+
+
+def span_rot_table(span_len):
+    """Rotary scale table of the span encoder (modeling.py:479-504: positions 1.., over max_len = 16)."""
+    return _cls_rot(rotary_coords_1d(span_len, False)[:, None] / 16.0)
 
 
 # ------------------------------------------------------------------------------------------------ CSR helpers

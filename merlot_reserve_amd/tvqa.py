@@ -21,16 +21,14 @@ validity code and one "rotary" row per position; the row at the first MASK of ev
 cross-entropy per stream against the same labels; hand-written backward in three stages (joint, audio, vision) through the
 same kernels as the pretraining step.  It is the one finetuning program that trains the audio tower.  Single stream, like VCR.
 """
-import copy
-
 import numpy as np
 import torch
 
 from . import ops
-from .engine import BF16, F32, I32, TowerState
+from .engine import BF16, F32, I32, PooledTower, TowerState
 from .finetune import FinetuneEngine, FinetuneGraphStep, MerlotReserveVCR, _model_of
 from .params import VOCAB, tvqa_param_specs
-from .planner import AUDIOSPAN, MASK, build_tvqa_plan, static_tables, tvqa_image_transpose
+from .planner import AUDIOSPAN, MASK, audio_tables, build_tvqa_plan, tvqa_image_transpose, vit_tables
 
 
 class TVQADims:
@@ -81,24 +79,12 @@ class TVQAEngine(FinetuneEngine):
         dev, H = self.dev, d.H
         z = lambda *s: torch.zeros(*s, dtype=BF16, device=dev)
         f = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
-        self.tv = TowerState(d.Nv * d.Sv, H, d.Lv, d.Nv, d.Sv, dev, saved=train)
-        self.ta = TowerState(d.Na * d.Sa, H, d.La, d.Na, d.Sa, dev, saved=train)
+        # the two input towers (the joint tower's "rotary" table depends on the batch's segment indices: it is part of the plan)
+        self.vision = PooledTower('vision_encoder', d.Nv, d.hw, d.pp3, d.Lv, H, vit_tables(d.gh, d.gw, d.pr, d.Nv), dev, train=train, saved=train)
+        self.audio = PooledTower('audio_encoder', d.Na, d.a_len, d.a_patch * 65, d.La, H, audio_tables(d.a_len, d.a_pool, d.Na), dev, train=train,
+                                 pad_input=True, saved=train)
+        self.tv, self.ta = self.vision.st, self.audio.st
         self.tj = TowerState(d.n * d.Sj, H, d.Lj, d.n, d.Sj, dev, saved=train)
-        # static tables: "rotary" / pool rows of the two input towers (the joint tower's "rotary" table depends on the batch's segment
-        # indices: it is part of the plan)
-        t = static_tables(d)
-        self.tables = {k: torch.as_tensor(t[k]).to(dev) for k in ('vit_rot', 'vit_pool_rows', 'audio_rot', 'audio_pool_rows')}
-        Gv, Ga = d.Nv * d.V, d.Na * d.a_tok
-        self.v_qin, self.v_q, self.v_po, self.imgs_seq = z(Gv, H), z(Gv, H), z(Gv, H), z(Gv, H)
-        self.v_k, self.v_v = z(self.tv.M, H), z(self.tv.M, H)
-        self.v_probs = f(Gv, d.nh, d.pr * d.pr)
-        self.v_cls = z(d.Nv, H)
-        self.a_pad_K = (d.a_patch * 65 + 7) // 8 * 8                  # 16-byte rows for the bf16 GEMM
-        self.a_in = z(d.Na * d.a_len, self.a_pad_K)
-        self.a_qin, self.a_q, self.a_po, self.audio_seq = z(Ga, H), z(Ga, H), z(Ga, H), z(Ga, H)
-        self.a_k, self.a_v = z(self.ta.M, H), z(self.ta.M, H)
-        self.a_probs = f(Ga, d.nh, d.a_pool)
-        self.a_cls = z(d.Na, H)
         self.pooled_h = z(d.n, H)
         self.logits = f(d.n, 8)                       # column 0 = the Dense(1) output; rows [0, A B) audio stream, [A B, 2 A B) text stream
         self.loss_acc = f(4)                          # [loss_audio, is_right_audio, loss_text, is_right_text]
@@ -111,41 +97,25 @@ class TVQAEngine(FinetuneEngine):
         # static transpose of the image-row tiling: every image row is read by the 2 A sequences of its example
         ip, ix = tvqa_image_transpose(d)
         self.visT = (torch.from_numpy(ip).to(dev), torch.from_numpy(ix).to(dev))
-        self.unpad_v, self.unpad_a = self._unpad_csr(d.Nv, d.Sv), self._unpad_csr(d.Na, d.Sa)
         self.d_pooled = z(d.n, H)
         self.dlogits = z(d.n, 8)
-        self.Dv, self.Da, self.Dj = z(self.tv.M, H), z(self.ta.M, H), z(self.tj.M, H)
-        self.d_imgs_seq, self.d_audio_seq = z(Gv, H), z(Ga, H)
-        self.d_v_cls, self.d_a_cls = z(d.Nv, H), z(d.Na, H)           # the cls outputs feed nothing: their gradients stay zero
-        # Single-stream program: the three towers are strictly sequential and share ONE scratch set -- but for the attention pool's d_k / d_v.
-        # Its backward leaves their CLS rows untouched (they must be zero), and the two input towers' CLS rows lie at different strides
-        # (every Sv-th / every Sa-th row): the audio tower's view of the set (sc_side) has a d_k / d_v pair of its own, 2 [Na Sa, H] bf16
+        self.Dj = z(self.tj.M, H)
+        # Single-stream program: the three towers are strictly sequential and share ONE scratch set (the cls outputs feed nothing: the
+        # towers' d_cls stay zero)
         Mmax = max(self.tv.M, self.ta.M, self.tj.M)
-        self.sc_main = self._make_scratch(Mmax, max(Gv, Ga), max(d.Nv * d.hw, d.Na * d.a_len), H, d.nh)
-        self.sc_side = copy.copy(self.sc_main)
-        self.sc_side.d_k, self.sc_side.d_v = z(self.ta.M, H), z(self.ta.M, H)
+        self.sc_main = self._make_scratch(Mmax, max(d.Nv * d.V, d.Na * d.a_tok), max(d.Nv * d.hw, d.Na * d.a_len), H, d.nh)
+        self.sc_side = self.sc_main
         self.cur = self.sc_main
 
     def build_plan(self, batch):
         return build_tvqa_plan(batch['textonly_seqs'], batch['audio_seqs'], self.d)
 
     def forward_device(self, images, audio_clips):
-        d, W, tv, ta, tj = self.d, self.W, self.tv, self.ta, self.tj
-        # vision tower on the B nseg frames (F:166-168)
-        self._images2d = images.reshape(d.Nv * d.hw, d.pp3)
-        self.fgemm(self._images2d, 'vision_encoder/embedding/kernel', tv.xin, bias=W['vision_encoder/embedding/bias'], row_map=(d.hw, d.Sv, 1))
-        self._tower_with_pool_forward(tv, 'vision_encoder/transformer', 'vision_encoder/seq_attnpool', self.tables['vit_rot'],
-                                      self.tables['vit_pool_rows'], self.v_qin, self.v_q, self.v_k, self.v_v, self.v_po, self.v_probs,
-                                      self.imgs_seq, self.v_cls)
-        # audio tower on the B nseg 3 clips (F:191-197): the stride-2 conv is a GEMM over 2 consecutive hops = 130 inputs
-        ops.pad_cols(audio_clips.reshape(d.Na * d.a_len, d.a_patch * 65), self.a_in)
-        self._audio2d = self.a_in[:, :d.a_patch * 65]
-        self.fgemm(self._audio2d, 'audio_encoder/embedding/kernel', ta.xin, bias=W['audio_encoder/embedding/bias'], row_map=(d.a_len, d.Sa, 1))
-        self._tower_with_pool_forward(ta, 'audio_encoder/transformer', 'audio_encoder/seq_attnpool', self.tables['audio_rot'],
-                                      self.tables['audio_pool_rows'], self.a_qin, self.a_q, self.a_k, self.a_v, self.a_po, self.a_probs,
-                                      self.audio_seq, self.a_cls)
+        d, W, tj = self.d, self.W, self.tj
+        self.vision.forward(self, images.reshape(d.Nv * d.hw, d.pp3))                        # the B nseg frames (F:166-168)
+        self.audio.forward(self, audio_clips.reshape(d.Na * d.a_len, d.a_patch * 65))        # the B nseg 3 clips (F:191-197)
         # joint tower on the 2 A B sequences (F:242-246)
-        ops.segment_sum([W['token_encoder/Embed_0/embedding'], self.audio_seq, self.imgs_seq], self._pl('joint_gather_indptr'),
+        ops.segment_sum([W['token_encoder/Embed_0/embedding'], self.audio.seq, self.vision.seq], self._pl('joint_gather_indptr'),
                         self._pl('joint_gather_idx'), tj.xin)
         self.encoder_forward(tj, 'joint_transformer', self._pl('joint_rot'), self._pl('joint_code'))
         ops.segment_sum([tj.xf], self._pl('pool_indptr'), self._pl('pool_idx'), self.pooled_h)       # F:250-251
@@ -181,15 +151,8 @@ class TVQAEngine(FinetuneEngine):
         self._flush_tower_reductions(tr)
         # the three transposes of the gather, each a fixed-order segment sum (no atomics)
         ops.segment_sum([Dj], self._pl('embT_indptr'), self._pl('embT_idx'), G['token_encoder/Embed_0/embedding'])
-        ops.segment_sum([Dj], self._pl('audT_indptr'), self._pl('audT_idx'), self.d_audio_seq)
-        ops.segment_sum([Dj], self.visT[0], self.visT[1], self.d_imgs_seq)
-
-    def backward_stage_audio(self):
-        self.cur = self.sc_side          # (the audio tower's view of the scratch set: its own d_k / d_v, see __init__)
-        try:
-            super().backward_stage_audio()
-        finally:
-            self.cur = self.sc_main
+        ops.segment_sum([Dj], self._pl('audT_indptr'), self._pl('audT_idx'), self.audio.d_seq)
+        ops.segment_sum([Dj], self.visT[0], self.visT[1], self.vision.d_seq)
 
     def loss_info(self):
         return self.info_from(self.loss_acc.tolist())

@@ -269,3 +269,32 @@ def test_transformer_encoder_arbitrary_mask_and_learned_pe(dev, bf16):
     got = model.joint_transformer(x, rotary_coords=None, is_valid=valid)['seq']
     ref = R.transformer_encoder(params2['joint_transformer'], torch.from_numpy(x), nl, rotary_coords=None, is_valid=torch.from_numpy(valid))['seq']
     assert relerr(got, ref) < tol, relerr(got, ref)
+
+
+def test_inference_towers_equal_the_fp32_engine_towers(dev):
+    """One tower definition (merlot_reserve_amd/towers.py) serves the inference API and the engines: on one perturbed parameter tree and the same fp32
+    images / audio, the fp32 inference model's vision_encoder / audio_encoder outputs equal the forward-only PretrainEngine(dtype=float32)'s tower
+    outputs bit for bit -- both issue the same fp32 kernels on the same operands (the bf16 engine reads transposed weight copies and may take another
+    GEMM route, so it is left out).  A characterization of the shared code, not a correctness check (the oracle tests above are that)."""
+    from merlot_reserve_amd.config import Dims
+    from merlot_reserve_amd.engine import PretrainEngine
+    from merlot_reserve_amd.params import ParamStore
+    from merlot_reserve_amd.planner import build_plan
+    from merlot_reserve_amd.synthetic import make_batch, make_draws
+    cfg, model, params = make_model(dev, False)
+    B, H = 2, 128
+    store = ParamStore(cfg, dev, seed=5)
+    store.load_tree(params)
+    batch = make_batch(cfg, B, seed=2, device=dev, float_dtype=torch.float32)
+    eng = PretrainEngine(cfg, B, store, dev, dtype=torch.float32)
+    assert eng.fwd_only
+    eng.forward(batch, plan=build_plan(batch, Dims(cfg, B), *make_draws(cfg, B, seed=2)))
+    model.bind(params)
+    d = eng.d
+    for enc, tower, x in ((model.vision_encoder, eng.vision, batch['images'].reshape(d.Nv, d.hw, d.pp3)),
+                          (model.audio_encoder, eng.audio, batch['audio_clips'].reshape(d.Na, d.a_raw, 65))):
+        out, st = enc(x), tower.st
+        assert x.dtype == torch.float32 and out['seq_attnpool'].numel() == tower.seq.numel() > 0
+        assert torch.equal(out['cls'], tower.cls), enc.prefix
+        assert torch.equal(out['seq'], st.xf.view(st.nseq, st.S, H)[:, 1:]), enc.prefix
+        assert torch.equal(out['seq_attnpool'].reshape(-1, H), tower.seq), enc.prefix
