@@ -391,6 +391,58 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(const G256Args ga) {
 // problems per launch: the weight gradients of TWO transformer layers fill the chip without split-K (216 tiles for the base
 // model) where one layer's four are 108; FOUR layers of the large model are 768 tiles = three full rounds where one layer's 192
 // leave a quarter of the CUs idle.  (TNArgs: gemm_plan.h)
+//
+// The k-tile's schedule (profiles/tn_kloop_before.txt, profiles/tn_kloop.txt).  A wave needs 48 ds_read_b64_tr_b16 and issues
+// 8 DMA pieces per k-tile, and in-kernel stamps showed its two memory sections (32 reads + 4 pieces, 16 reads + 4 pieces, each drained with
+// lgkmcnt(0)) at 870-960 and 670-680 clocks beside the partner group's 512-clock MFMA blocks: the sections, not the matrix pipe, set the k-tile.
+// So the sections carry only what nothing else can:
+//     phase 0 memory  B (16 reads) + the kk = 0 halves of A0 (8)  | A pieces 0-1 of k-tile t+2 | lgkmcnt(8): the B reads are back   s_barrier
+//     phase 0 MFMA    the kk = 1 halves of A0 (8 reads) | 16 MFMAs kk = 0 | A1 kk = 0 in place (8) | 16 MFMAs kk = 1 | A1 kk = 1 in place (8)  s_barrier
+//     phase 1 memory  A pieces 2-3 and the four B pieces of k-tile t+2 | lgkmcnt(0) | the counted vmcnt: k-tile t+1 has landed           s_barrier
+//     phase 1 MFMA    32 MFMAs A1 x B                                                                                                   s_barrier
+// 24 of the 48 reads land under the wave's own MFMAs behind counted waits (LDS data returns in issue order).  Every accumulator still receives
+// kk = 0 before kk = 1 of every k-tile, so the outputs are those of the two-drain schedule bit for bit.
+// Ring safety, by construction as before: every LDS read that a later DMA overwrites is retired ahead of a barrier its wave passes before any wave
+// issues that DMA.  B (2 stages: k-tile t+2 overwrites k-tile t in phase 1): all B reads sit in phase 0's memory section and are retired by its
+// lgkmcnt(8) ahead of the barrier (the B reads are issued first; 8 later reads may be outstanding).  A (3 stages: k-tile t+3 overwrites k-tile t in
+// the phase 0 / phase 1 memory sections of k-tile t+1): the last reads of k-tile t, A1 in phase 0's MFMA section, are retired by phase 1's lgkmcnt(0)
+// ahead of its barrier -- the barrier behind which the OTHER group enters its next phase 0.
+
+// -DMR_TN_STAMPS: a DIAGNOSTIC build (scripts/tn_kloop_stamps.py).  Every wave reads the shader clock at the section boundaries of a k-tile and adds
+// the differences into scalar sums; lane 0 of wave 0 (group 0) and of wave 4 (group 1) of the first 256 workgroups store them behind the k-loop into a
+// buffer of their own, which the launcher prints.  The stamp's lgkmcnt(0) drains the fragment reads a section leaves in flight: read the SHARES of such
+// a build, never its run time.  Segments: 0 memory section 0 | 1 barrier | 2 MFMA block 0 | 3 barrier | 4 memory section 1 | 5 ring wait | 6 barrier |
+// 7 MFMA block 1 | 8 barrier.
+#ifdef MR_TN_STAMPS
+#include <stdio.h>
+constexpr int TN_NSEG = 9;
+__device__ unsigned long long tn_stamp_sums[256][2][TN_NSEG];
+#define TN_STAMP_NOW(v_)                                                                                                \
+    do {                                                                                                                \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v_)::"memory");                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+    } while (0)
+#define TN_STAMP_INIT()                                                                                                 \
+    unsigned long long st_prev, st_sum[TN_NSEG] = {};                                                                   \
+    TN_STAMP_NOW(st_prev)
+#define TN_STAMP(seg_)                                                                                                  \
+    do {                                                                                                                \
+        unsigned long long now_;                                                                                        \
+        TN_STAMP_NOW(now_);                                                                                             \
+        st_sum[seg_] += now_ - st_prev;                                                                                 \
+        st_prev = now_;                                                                                                 \
+    } while (0)
+#define TN_STAMP_STORE()                                                                                                \
+    do {                                                                                                                \
+        if (blockIdx.x < 256 && (wave & 3) == 0 && lane == 0)                                                           \
+            for (int k_ = 0; k_ < TN_NSEG; ++k_) tn_stamp_sums[blockIdx.x][wr][k_] = st_sum[k_];                        \
+    } while (0)
+#else
+#define TN_STAMP_INIT() do {} while (0)
+#define TN_STAMP(seg_) do {} while (0)
+#define TN_STAMP_STORE() do {} while (0)
+#endif
 
 __global__ __launch_bounds__(512, 2) void gemm3_tn_kernel(const TNArgs ta) {
     constexpr int NJ = 4, STAGE = 64 * 512, NSTAGE_A = 3, NSTAGE_B = 2, OFF_B = NSTAGE_A * STAGE, WAITN = 8;
@@ -421,7 +473,7 @@ __global__ __launch_bounds__(512, 2) void gemm3_tn_kernel(const TNArgs ta) {
     }
     int ik = 0, ista = 0, istb = 0;
     bool issued = false;
-#define TN_ISSUE_A()                                                                                                    \
+#define TN_ISSUE_A_LO()                                                                                                 \
     do {                                                                                                                \
         issued = ik < nkt;                                                                                              \
         if (issued) {                                                                                                   \
@@ -429,10 +481,22 @@ __global__ __launch_bounds__(512, 2) void gemm3_tn_kernel(const TNArgs ta) {
             const unsigned sa = (unsigned)ik * a_step;                                                                  \
             MR_DMA(ra, MR_LDS_PTR(void, st_), 16, ao[0], sa, 0, 0);                                                     \
             MR_DMA(ra, MR_LDS_PTR(void, st_ + 1024), 16, ao[1], sa, 0, 0);                                              \
+        }                                                                                                               \
+    } while (0)
+#define TN_ISSUE_A_HI()                                                                                                 \
+    do {                                                                                                                \
+        if (issued) {                                                                                                   \
+            char* st_ = smem + ista * STAGE + wave * 4096;                                                              \
+            const unsigned sa = (unsigned)ik * a_step;                                                                  \
             MR_DMA(ra, MR_LDS_PTR(void, st_ + 2048), 16, ao[2], sa, 0, 0);                                              \
             MR_DMA(ra, MR_LDS_PTR(void, st_ + 3072), 16, ao[3], sa, 0, 0);                                              \
             ista = (ista == NSTAGE_A - 1) ? 0 : ista + 1;                                                               \
         }                                                                                                               \
+    } while (0)
+#define TN_ISSUE_A()                                                                                                    \
+    do {                                                                                                                \
+        TN_ISSUE_A_LO();                                                                                                \
+        TN_ISSUE_A_HI();                                                                                                \
     } while (0)
 #define TN_ISSUE_B()                                                                                                    \
     do {                                                                                                                \
@@ -459,51 +523,81 @@ __global__ __launch_bounds__(512, 2) void gemm3_tn_kernel(const TNArgs ta) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     int csa = 0, csb = 0;
+    TN_STAMP_INIT();
     for (int t = 0; t < nkt; ++t) {
         const char* As = smem + csa * STAGE;
         const char* Bs = smem + OFF_B + csb * STAGE;
         bf16x8 a[4][2], b[NJ][2];
-        auto read_a = [&](int half) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) a[i][kk] = frag<true, 256, 64>(As, wr * 128 + half * 64 + i * 16, kk, lane);
-        };
-        auto mfmas = [&](int half) {
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j)
-                        acc[half * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j][kk], a[i][kk], acc[half * 4 + i][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-        };
-        // phase 0: A0 x B; every read of the phase is retired AHEAD of the barrier (phase 1 restages B; lgkmcnt counts to 15 only)
+        // ---------------- phase 0, memory section: B (16 reads), the kk = 0 halves of A0 (8 reads), two A pieces of k-tile t+2 ----------------
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) b[j][kk] = frag<true, 256, 64>(Bs, wc * 64 + j * 16, kk, lane);
-        read_a(0);
+        __builtin_amdgcn_sched_barrier(0);      // B before A: the counted waits below rely on the issue order
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i][0] = frag<true, 256, 64>(As, wr * 128 + i * 16, 0, lane);
         __builtin_amdgcn_sched_barrier(0);
-        TN_ISSUE_A();
-        G3_LGKM(0);
+        TN_ISSUE_A_LO();
+        G3_LGKM(8);                             // every B read is back AHEAD of the barrier (phase 1 restages B); the 8 A0 reads may still fly
+        TN_STAMP(0);
         G3_BARRIER();
-        mfmas(0);
-        G3_BARRIER();
-        // phase 1: A1 x B
-        read_a(1);
+        TN_STAMP(1);
+        // ---------------- phase 0, MFMA section: A0 x B, kk = 0 then kk = 1 (each accumulator's k order is that of the two-drain schedule).
+        // Reads land under the wave's own MFMAs: the kk = 1 halves of A0 are requested first and waited for 16 MFMAs later; the A1
+        // fragments replace the A0 fragments IN PLACE, each half requested behind the last MFMA that read its registers.  LDS data returns
+        // in issue order, and behind the fragments a wait is for exactly 8 reads are outstanding. ----------------
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i][1] = frag<true, 256, 64>(As, wr * 128 + i * 16, 1, lane);
         __builtin_amdgcn_sched_barrier(0);
+        G3_LGKM(8);                             // A0, kk = 0
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j][0], a[i][0], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i][0] = frag<true, 256, 64>(As, wr * 128 + 64 + i * 16, 0, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        G3_LGKM(8);                             // A0, kk = 1
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j][1], a[i][1], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i][1] = frag<true, 256, 64>(As, wr * 128 + 64 + i * 16, 1, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(0);
+        TN_STAMP(2);
+        G3_BARRIER();
+        TN_STAMP(3);
+        // ---------------- phase 1, memory section: no fragment reads of its own -- the other two A pieces and the four B pieces of k-tile t+2.
+        // The A1 reads are retired ahead of the barrier (behind it the other group's next phase 0 restages A) ----------------
+        TN_ISSUE_A_HI();
         TN_ISSUE_B();
         G3_LGKM(0);
+        TN_STAMP(4);
         if (issued) wait_vmcnt<WAITN>(); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        TN_STAMP(5);
         G3_BARRIER();
-        mfmas(1);
+        TN_STAMP(6);
+        // ---------------- phase 1, MFMA section: A1 x B ----------------
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j][kk], a[i][kk], acc[4 + i][j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+        TN_STAMP(7);
         G3_BARRIER();
+        TN_STAMP(8);
         csa = (csa == NSTAGE_A - 1) ? 0 : csa + 1;
         csb = (csb == NSTAGE_B - 1) ? 0 : csb + 1;
     }
+    TN_STAMP_STORE();
     if (wr == 0) G3_BARRIER();          // pairs with group 1's last barrier
 
     // epilogue: bf16 stores, widened to 16 B (see the NT kernel's store_pair)
@@ -555,4 +649,15 @@ void mr_gemm3_launch(const g256::G256Args& ga, int bn, int mode, int ph, int64_t
 
 void mr_gemm3_tn_launch(const g3::TNArgs& ta, int64_t tiles, hipStream_t s) {
     hipLaunchKernelGGL(g3::gemm3_tn_kernel, dim3((unsigned)tiles), dim3(512), 0, s, ta);
+#ifdef MR_TN_STAMPS
+    // diagnostic build: one line per stamped wave and launch on stderr -- workgroup, group, k-tiles, the nine segment sums in shader clocks
+    static unsigned long long host_sums[256][2][g3::TN_NSEG];
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpyFromSymbol(host_sums, HIP_SYMBOL(g3::tn_stamp_sums), sizeof(host_sums)) != hipSuccess) return;
+    for (int w = 0; w < (tiles < 256 ? (int)tiles : 256); ++w)
+        for (int g = 0; g < 2; ++g) {
+            fprintf(stderr, "TNSTAMP %d %d %d", w, g, (ta.K + 63) >> 6);
+            for (int k = 0; k < g3::TN_NSEG; ++k) fprintf(stderr, " %llu", host_sums[w][g][k]);
+            fprintf(stderr, "\n");
+        }
+#endif
 }
