@@ -1,5 +1,6 @@
-"""Builds libmreserve_hip.so, libmreserve_media.so and libmreserve_zeroshot.so (gfx950) in-tree with hipcc.  No torch extension machinery: the
-libraries are plain C-ABI shared objects (include/mreserve_hip.h, include/mreserve_media.h, include/mreserve_zeroshot.h) loaded through ctypes."""
+"""Builds libmreserve_hip.so, libmreserve_media.so, libmreserve_zeroshot.so and libmreserve_ingest.so (gfx950) in-tree with hipcc.  No torch extension
+machinery: the libraries are plain C-ABI shared objects (include/mreserve_hip.h, include/mreserve_media.h, include/mreserve_zeroshot.h,
+include/mreserve_ingest.h) loaded through ctypes."""
 import os
 import subprocess
 import sys
@@ -21,7 +22,7 @@ LIB = os.path.join(HERE, 'libmreserve_hip.so')
 # scalar as well; the bf16 GEMM files keep their packed epilogues (3.2 ms of the step) and are held to bit-stability under that neighbour by the test.
 EXTRA_FLAGS = {'attention.hip': ['-fno-slp-vectorize'], 'layernorm.hip': ['-fno-slp-vectorize'], 'rowops.hip': ['-fno-slp-vectorize'],
                'adam.hip': ['-fno-slp-vectorize', '-ffp-contract=off'], 'f32bwd.hip': ['-fno-slp-vectorize'], 'f32path.hip': ['-fno-slp-vectorize'],
-               'media.hip': ['-fno-slp-vectorize'], 'zeroshot.hip': ['-fno-slp-vectorize']}
+               'media.hip': ['-fno-slp-vectorize'], 'zeroshot.hip': ['-fno-slp-vectorize'], 'ingest.hip': ['-fno-slp-vectorize']}
 # The hazard at instruction level (scripts/micro/pk_probe.hip, scripts/pk_probe.py): v_pk_add_f32 / v_pk_fma_f32 (any packed fp32 arithmetic) with an
 # `op_sel:[..1..]` source -- the LOW result element reading the HIGH register of a source pair -- returns wrong values in lanes 48-63 of a wave
 # while another kernel's MFMA waves are resident on its SIMD (0 mismatches alone; op_sel_hi, neg_lo / neg_hi, v_pk_mov_b32 op_sel are unaffected).
@@ -42,6 +43,12 @@ MEDIA_HIP_FILES = [f for f in MEDIA_SOURCES if f.endswith('.hip')]
 ZEROSHOT_LIB = os.path.join(HERE, 'libmreserve_zeroshot.so')
 ZEROSHOT_SOURCES = ['zeroshot.hip']
 ZEROSHOT_HIP_FILES = [f for f in ZEROSHOT_SOURCES if f.endswith('.hip')]
+# libmreserve_ingest.so (include/mreserve_ingest.h, symbols mri_*): PCM resampling / downmix and black-bar bounds, a fourth library on the same
+# terms: its own symbols only, fp32 code built scalar, scanned, no spill allowance.
+INGEST_LIB = os.path.join(HERE, 'libmreserve_ingest.so')
+INGEST_SOURCES = ['ingest.hip']
+INGEST_HIP_FILES = [f for f in INGEST_SOURCES if f.endswith('.hip')]
+LIBS = (LIB, MEDIA_LIB, ZEROSHOT_LIB, INGEST_LIB)
 # Register spills (metadata .vgpr_spill_count / .sgpr_spill_count of every kernel in the device assembly): a spill inside a k-loop costs more than any
 # schedule gains (gemm4<256,0> with 183 spilled registers: 299 vs 91 us), so build() FAILS on a kernel with spilled vector registers unless it is
 # listed here with the number it is known to carry and the reason it is tolerated.  {regex on the demangled-ish symbol: (max spilled VGPRs, why)}
@@ -75,20 +82,20 @@ def _asm_path(src):
 
 
 def _needs_build():
-    if not all(os.path.exists(p) for p in (LIB, MEDIA_LIB, ZEROSHOT_LIB)):
+    if not all(os.path.exists(p) for p in LIBS):
         return True
     if not os.path.exists(STAMP):
         # a library that travelled without its build/ directory (the GPU box's snapshot carries both; a bare copy does not): trust the mtimes
         pass
     elif open(STAMP).read() != _flag_stamp():
         return True
-    t = min(os.path.getmtime(p) for p in (LIB, MEDIA_LIB, ZEROSHOT_LIB))
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, '..', 'include', h) for h in ('mreserve_hip.h', 'mreserve_media.h', 'mreserve_zeroshot.h')]
+    t = min(os.path.getmtime(p) for p in LIBS)
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, '..', 'include', h) for h in ('mreserve_hip.h', 'mreserve_media.h', 'mreserve_zeroshot.h', 'mreserve_ingest.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def _asm_stale():
-    return any(not os.path.exists(_asm_path(f)) or os.path.getmtime(_asm_path(f)) < os.path.getmtime(os.path.join(CSRC, f)) for f in HIP_FILES + MEDIA_HIP_FILES + ZEROSHOT_HIP_FILES)
+    return any(not os.path.exists(_asm_path(f)) or os.path.getmtime(_asm_path(f)) < os.path.getmtime(os.path.join(CSRC, f)) for f in HIP_FILES + MEDIA_HIP_FILES + ZEROSHOT_HIP_FILES + INGEST_HIP_FILES)
 
 
 def scan_packed_op_sel(files=None):
@@ -186,19 +193,19 @@ def build(force=False, verbose=True):
     if not force and not _needs_build():
         return LIB
     import json
-    all_hip = HIP_FILES + MEDIA_HIP_FILES + ZEROSHOT_HIP_FILES
+    all_hip = HIP_FILES + MEDIA_HIP_FILES + ZEROSHOT_HIP_FILES + INGEST_HIP_FILES
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     bdir = os.path.join(HERE, 'build')
     os.makedirs(bdir, exist_ok=True)
-    objs, media_objs, zeroshot_objs, queue, running, failed = [], [], [], [], [], []
-    for src in SOURCES + MEDIA_SOURCES + ZEROSHOT_SOURCES:
+    objs, media_objs, zeroshot_objs, ingest_objs, queue, running, failed = [], [], [], [], [], [], []
+    for src in SOURCES + MEDIA_SOURCES + ZEROSHOT_SOURCES + INGEST_SOURCES:
         stem = src.rsplit('.', 1)[0]
         obj = os.path.join(bdir, stem + '.o')
         cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17'] + EXTRA_FLAGS.get(src, []) + ['-x', 'hip', '-c', os.path.join(CSRC, src), '-o', obj]
         if src.endswith('.hip'):
             cmd.append('--save-temps=obj')          # leaves <stem>-hip-amdgcn-amd-amdhsa-gfx950.s: the device assembly OF THIS OBJECT, for the scans
         queue.append((src, cmd))
-        (media_objs if src in MEDIA_SOURCES else zeroshot_objs if src in ZEROSHOT_SOURCES else objs).append(obj)
+        (media_objs if src in MEDIA_SOURCES else zeroshot_objs if src in ZEROSHOT_SOURCES else ingest_objs if src in INGEST_SOURCES else objs).append(obj)
     while queue or running:
         while queue and len(running) < JOBS:
             src, cmd = queue.pop(0)
@@ -234,10 +241,12 @@ def build(force=False, verbose=True):
     subprocess.check_call(cmd)
     cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-z,defs', '-Wl,--version-script=' + os.path.join(CSRC, 'zeroshot_exports.map'), '-o', ZEROSHOT_LIB] + zeroshot_objs
     subprocess.check_call(cmd)
+    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-Wl,-z,defs', '-Wl,--version-script=' + os.path.join(CSRC, 'ingest_exports.map'), '-o', INGEST_LIB] + ingest_objs
+    subprocess.check_call(cmd)
     with open(STAMP, 'w') as f:
         f.write(_flag_stamp())
     if verbose:
-        print(f'built {LIB}, {MEDIA_LIB} and {ZEROSHOT_LIB}', file=sys.stderr)
+        print(f'built {LIB}, {MEDIA_LIB}, {ZEROSHOT_LIB} and {INGEST_LIB}', file=sys.stderr)
     return LIB
 
 

@@ -8,7 +8,7 @@
                      no flip, zero padding) and space_to_depth in one pass
 
 The tables (window, twiddles, filterbank, filter taps) are made here in float64, rounded once to float32 and uploaded once per device.  File
-decoding (ffmpeg) and black-bar trimming stay outside the package."""
+decoding (ffmpeg) stays outside the package; PCM resampling and black-bar trimming are merlot_reserve_amd.ingest."""
 import numpy as np
 import torch
 

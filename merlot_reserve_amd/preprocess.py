@@ -1,11 +1,13 @@
 """`mreserve.preprocess` (mreserve/preprocess.py:121-156, 247-271, 463-551): what turns decoded media into the arrays
-`MerlotReserve.embed_video` takes.  File decoding (ffmpeg / ffprobe) and black-bar trimming (preprocess.py:27-118) are out of
-scope; the two numeric transforms behind them run on the GPU (merlot_reserve_amd.media): uint8 frames of any size become
-patches, waveforms become log-mel spectrograms.  Frames that already are float arrays at the target resolution, ready
-patches and ready [3, 60, 65] spectrograms are taken as before.
+`MerlotReserve.embed_video` takes.  File decoding (ffmpeg / ffprobe) is out of scope; everything behind it runs on the GPU: PCM of any
+rate and channel layout becomes the mono 22050 Hz waveform and black bars are trimmed (merlot_reserve_amd.ingest), uint8 frames of
+any size become patches and waveforms become log-mel spectrograms (merlot_reserve_amd.media).  Frames that already are float arrays
+at the target resolution, ready patches and ready [3, 60, 65] spectrograms are taken as before.
 
   make_spectrogram(s)            preprocess.py:121-156   log-mel of a 5 s waveform, three [60, 65] clips
-  segments_from_decoded          preprocess.py:247-271   the array half of video_to_segments
+  segments_from_decoded          preprocess.py:247-271   the array half of video_to_segments (mono 22050 Hz waveform, frames as they are)
+  segments_from_pcm              preprocess.py:216-271   the same from PCM as decoders give it: downmix, resampling, black-bar trimming
+  segments_from_decoded_zero_shot  preprocess.py:312-346 the array half of video_to_segments_zero_shot
   preprocess_image_to_patches    preprocess.py:464-481   resize_and_pad (bilinear, antialiased) + space_to_depth
   patchify                       preprocess.py:478-479   tf.nn.space_to_depth(img, 16) + reshape -> [h*w, 768], patch vector
                                                           order (dy, dx, c) -- the same order as pretrain/dataloader.py:83-84
@@ -35,9 +37,11 @@ def __getattr__(name):
 
 def video_to_segments(*args, **kwargs):
     """mreserve/preprocess.py:352-460 decodes a video file with ffmpeg / librosa into frames and mel spectrograms: media
-    decoding is outside this package -- pass the decoded frames and waveform to segments_from_decoded."""
-    raise NotImplementedError('video decoding (ffmpeg) is out of scope: decode the frames (uint8 [n, H, W, 3]) and the mono 22050 Hz '
-                              'waveform yourself, call segments_from_decoded(frames, waveform) and then preprocess_video')
+    decoding is outside this package -- pass the decoded frames and audio to segments_from_pcm (PCM at the file's own
+    rate and channel count) or segments_from_decoded (a mono 22050 Hz waveform)."""
+    raise NotImplementedError('video decoding (ffmpeg) is out of scope: decode the frames (uint8 [n, H, W, 3]) and the audio yourself, call '
+                              'segments_from_pcm(frames, pcm, sr) with the PCM as decoded, or segments_from_decoded(frames, waveform) with a '
+                              'mono 22050 Hz waveform, and then preprocess_video')
 
 
 def _is_u8(x):
@@ -120,6 +124,104 @@ def segments_from_decoded(frames, waveform, sr=22050, time_interval=5.0, segment
     for i, (frame_i, ts_i) in enumerate(zip(frames, times)):
         ts_i['frame'] = frame_i
         ts_i['spectrogram'] = specs[i]
+        ts_i['idx'] = i
+    return times
+
+
+def _segment_times(n, time_interval, segment_start_time):
+    times, st = [], segment_start_time
+    for _ in range(n):
+        et = st + time_interval
+        times.append({'start_time': st, 'end_time': et, 'mid_time': (st + et) / 2.0})
+        st = et
+    return times
+
+
+def _pad_to(wave, length):
+    """a 1-D tensor zero-padded at the end to at least `length` samples"""
+    import torch
+    if wave.numel() >= length:
+        return wave
+    return torch.cat([wave, torch.zeros(length - wave.numel(), dtype=wave.dtype, device=wave.device)])
+
+
+def segments_from_pcm(frames, pcm, sr, time_interval=5.0, segment_start_time=0.0, trim_black_bars=True, blackbar_threshold=32,
+                      max_perc_to_trim=.2, channels_last=None, device=None):
+    """What video_to_segments does with its decoded inputs (preprocess.py:216-271), from media as decoders give it: frames uint8
+    [n, H, W, 3] (one per segment, taken at its middle) and `pcm`, int16 or float32 at `sr` Hz, [N], [C, N] or [N, C] (ingest.resample_mono)
+    -> the reference's list of dicts, as segments_from_decoded returns it.
+
+      audio    ffmpeg's `-ac 1 -ar 22050` is ingest.resample_mono; the waveform is divided by max(peak, 1) on the device (a float32 division, no
+               host round trip), zero-padded to int(22050 * last end), cut at int(22050 * start) : int(22050 * end); one make_spectrograms launch
+      frames   ingest.trim_black_bars over the whole stack (extract_frames_from_video, :115-118), or untouched with trim_black_bars=False
+
+    With `device` the frames and spectrograms stay there.  One deviation: the reference's waveform passes through an int16 WAV file between
+    ffmpeg and numpy, so its resampled samples are rounded to integers; here they stay float32."""
+    import torch
+    from . import ingest
+    n = len(frames)
+    times = _segment_times(n, time_interval, segment_start_time)
+    if n == 0:
+        return times
+    wave, peak = ingest.resample_mono(pcm, sr, channels_last=channels_last, device=device)
+    wave = _pad_to(wave / torch.clamp_min(peak, 1.0), int(ingest.SR * max(t['end_time'] for t in times)))
+    cuts = [wave[int(ingest.SR * t['start_time']):int(ingest.SR * t['end_time'])] for t in times]
+    if len({len(c) for c in cuts}) != 1:
+        raise ValueError(f'segments of unequal length {sorted({len(c) for c in cuts})}: choose time_interval and segment_start_time so that sr * time is whole')
+    specs = make_spectrograms(torch.stack(cuts), playback_speed=1, sr=ingest.SR, device=device)
+    if isinstance(frames, (list, tuple)):
+        frames = torch.stack(list(frames)) if isinstance(frames[0], torch.Tensor) else np.stack(frames)
+    if device is not None:
+        frames = torch.as_tensor(frames).to(device)
+    if trim_black_bars:
+        frames = ingest.trim_black_bars(frames, blackbar_threshold=blackbar_threshold, max_perc_to_trim=max_perc_to_trim, device=device)
+    for i, (frame_i, ts_i) in enumerate(zip(frames, times)):
+        ts_i['frame'] = frame_i
+        ts_i['spectrogram'] = specs[i]
+        ts_i['idx'] = i
+    return times
+
+
+def segments_from_decoded_zero_shot(frames, waveform, times, sr=22050, device=None):
+    """The array half of video_to_segments_zero_shot (preprocess.py:312-346; its consumer is demo/zero_shot_ek/extract_ek100_feat.py): `times` is
+    a list of {'start_time', 'end_time', 'mid_time'}, frames one per entry, waveform mono at 22050 Hz as for segments_from_decoded -- from raw PCM:
+
+        wave, _ = ingest.resample_mono(pcm, file_rate, device=dev)
+        segs = segments_from_decoded_zero_shot(ingest.trim_black_bars(frames), wave, times, device=dev)
+
+    The waveform is divided by max(|w|.max(), 1) and zero-padded to the last end.  A segment shorter than 5 s is centred in zero padding of
+    left = int((sr * 5.0 - len) / 2) and right = int(sr * 5.0 - len - left) samples; one of 5 s or more is cut at
+    int(sr * (mid - 2.5)) : int(sr * (mid + 2.5)).  A cut whose length does not give 188 spectrogram rows raises the reference's ValueError; cuts
+    are grouped by length, one launch per distinct length.  Returns new dicts with 'frame', 'spectrogram' and 'idx' added; frames are not touched."""
+    import torch
+    times = [dict(t) for t in times]
+    if not times:
+        return times
+    if not isinstance(waveform, torch.Tensor):
+        waveform = torch.from_numpy(np.asarray(waveform).astype('float32'))
+    w = waveform.to(torch.float32)
+    w = w / torch.clamp_min(w.abs().max(), 1.0) if w.numel() else w
+    w = _pad_to(w, int(sr * max(t['end_time'] for t in times)))
+    window = sr * 5.0                                                     # samples of a 5 s window, a float as in the reference
+    cuts = []
+    for ts in times:
+        if ts['end_time'] - ts['start_time'] < 5.0:                       # shorter than the window: centred in zeros
+            cut = w[int(sr * ts['start_time']):int(sr * ts['end_time'])]
+            left = int((window - len(cut)) / 2)
+            right = int(window - len(cut) - left)
+            cut = torch.cat([w.new_zeros(left), cut, w.new_zeros(right)])
+        else:                                                             # 5 s or more: the window around the middle
+            cut = w[int(sr * (ts['mid_time'] - 2.5)):int(sr * (ts['mid_time'] + 2.5))]
+        cuts.append(cut)
+    groups = {}
+    for i, c in enumerate(cuts):
+        groups.setdefault(len(c), []).append(i)
+    for idx in groups.values():
+        specs = make_spectrograms(torch.stack([cuts[i] for i in idx]), playback_speed=1, sr=sr, device=device)
+        for i, spec in zip(idx, specs):
+            times[i]['spectrogram'] = spec
+    for i, (frame_i, ts_i) in enumerate(zip(frames, times)):
+        ts_i['frame'] = frame_i
         ts_i['idx'] = i
     return times
 

@@ -3,7 +3,8 @@
 from merlot_reserve_amd import preprocess as _p
 from merlot_reserve_amd.preprocess import (END, LTOVPOOL, MASK, MASKAUDIO, PADDING, RESETCTX, START, make_spectrogram,   # noqa: F401
                                            make_spectrograms, patchify, preprocess_image_to_patches, preprocess_video,
-                                           segments_from_decoded, video_to_segments)
+                                           segments_from_decoded, segments_from_decoded_zero_shot, segments_from_pcm,
+                                           video_to_segments)
 
 
 def __getattr__(name):
